@@ -19,7 +19,11 @@ that reference.
    clips -- no collective on the data path; weak scaling.  `--shard slices`: ONE set of frames whose slice chains are split
    over the ranks (sharding.slices_for_rank), outputs gathered on rank 0 after the timed region; strong scaling.)
 
-Prints ONE JSON line on rank 0 (metric/value/... + "roofline" + "cpu_baseline" + transfer / chain-count / split-match detail).
+Prints ONE JSON line on rank 0 (metric/value/... + "roofline").  A plain run sets up, warms up, times the steps and prints it;
+`--full` adds what takes runs of its own: "cpu_baseline" + split-match detail (the in-repo oracle on the host), transfers,
+the chain-count sweep, the SliceMode-0 point and, for the default intra command, a short lowdelay_P leg under "ldp".
+`--dump-outputs DIR`: after the timed steps, a fixed seeded sample of the CTUs the last step decided (fcu_ctu_out fields and
+reconstructed samples) as DIR/*.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -125,6 +129,40 @@ def cpu_leg(make_encoder, first_ctu, gpu_lookup, budget_s, label):
     return n, dt, same, total, label
 
 
+DUMP_CTUS = 512                     # CTUs of the last timed step written by --dump-outputs: about 40 MB
+
+
+def dump_outputs(out_dir, pkg, torch, np, chain_list, last, outs, recs, W, H):
+    """What the last timed step handed its caller, for a fixed seeded sample of its CTUs (`last`: (chain, CTU address)
+    pairs): every fcu_ctu_out field as ctu_<field>.npy (float32; total_cost / total_dist / total_bits / total_bins float64),
+    the reconstructed 64x64 luma / 32x32 chroma samples of the CTU as rec_y / rec_cb / rec_cr.npy (float32, -1 outside the
+    picture; not written when `recs` is None) and sample.npy: frame seed, QP and CTU address of each row."""
+    rng = np.random.default_rng(12345)
+    pick = sorted(rng.choice(len(last), size=min(DUMP_CTUS, len(last)), replace=False).tolist())
+    rows = [(chain_list[last[i][0]], last[i][1]) for i in pick]
+    nb = pkg.engine.CTU_OUT_BYTES
+    raw = torch.stack([outs[(seed, qp)][addr * nb:(addr + 1) * nb] for (seed, qp, _), addr in rows]).cpu().numpy()
+    rec_dtype = np.dtype(pkg.engine.CtuOut)
+    assert rec_dtype.itemsize == nb
+    recs_np = raw.view(rec_dtype).reshape(len(rows))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in rec_dtype.names:
+        v = recs_np[name]
+        np.save(os.path.join(out_dir, f"ctu_{name}.npy"), v.astype(np.float64 if v.ndim == 1 else np.float32))
+    np.save(os.path.join(out_dir, "sample.npy"), np.array([[seed, qp, addr] for (seed, qp, _), addr in rows], dtype=np.float64))
+    if recs is None:
+        return
+    wc = (W + 63) // 64
+    for p, name in enumerate(("y", "cb", "cr")):
+        s = 64 >> (1 if p else 0)
+        blk = np.full((len(rows), s, s), -1, dtype=np.float32)
+        for r, ((seed, qp, _), addr) in enumerate(rows):
+            y0, x0 = (addr // wc) * s, (addr % wc) * s
+            b = recs[(seed, qp)][p][y0:y0 + s, x0:x0 + s].cpu().numpy()
+            blk[r, :b.shape[0], :b.shape[1]] = b
+        np.save(os.path.join(out_dir, f"rec_{name}.npy"), blk)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -150,8 +188,14 @@ def parse_args(argv=None):
                     help="fork state of the timed steps (intra).  training (default, the headline metric): exhaustive RDO.  testing: "
                          "the fork's Naive pruning; OBF maps from the device pre-pass, the first warm-up step runs in the Verifying "
                          "state and its counters set the per-depth switches (SetDecisionSwitch)")
-    ap.add_argument("--no-ldp-leg", action="store_true", help="default intra run on one GPU: skip the short lowdelay_P measurement reported under \"ldp\" in the same JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--no-ldp-leg", action="store_true", help="--full, default intra run on one GPU: skip the short lowdelay_P measurement reported under \"ldp\" in the same JSON line")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline + split match, transfers, chain-count sweep, SliceMode-0 point and the lowdelay_P leg "
+                    "(off: set up, warm up, time the steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed seeded sample of what the last timed step decided as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def run(args, emit=True):
@@ -189,7 +233,11 @@ def run(args, emit=True):
     # region); only the full search of lowdelay_P, 5x slower, keeps to 2 CTUs per step
     cps = args.ctus_per_step or (2 if (ldp and not args.fast_search) else max(1, sl // (args.warmup + args.steps)))
     walked = (args.warmup + args.steps) * cps
-    assert walked <= sl, "bench walks past the end of the slice"
+    assert cps <= sl, "more CTUs per step than a slice holds"
+    # launches that walk a slice once; a longer run (more than `sl` warm-up + timed steps, or --ctus-per-step too large for
+    # them) starts every chain at the first CTU of its slice again after each pass, outside the timed region
+    per_pass = sl // cps
+    span = lambda g: ((g % per_pass) * cps, (g % per_pass) * cps + cps)     # CTUs [a, b) of a slice decided by launch g
     strong = args.shard == "slices" and world > 1
     # chains: (frame seed, qp, slice).  weak scaling: every rank owns its own frames; --shard slices: all ranks see the same
     # frames and each owns whole slices of them (no slice is shared, no collective on the data path)
@@ -268,7 +316,22 @@ def run(args, emit=True):
         switches = pkg.engine.decision_switch(ver)
         for ci, (seed, qp, k) in enumerate(chain_list):
             eng.set_decision(ci, pkg.engine.TESTING, obf[seed], *switches)
-    for _ in range(args.warmup - (1 if switches is not None else 0)):
+
+    def restart():
+        """every chain back to the first CTU of its slice (a run longer than one pass); returns the seconds it took"""
+        eng.sync()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for ci in range(n_chains):
+            bind(ci)
+            if switches is not None:
+                eng.set_decision(ci, pkg.engine.TESTING, obf[chain_list[ci][0]], *switches)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t1
+
+    for g in range(1 if switches is not None else 0, args.warmup):
+        if g and g % per_pass == 0:
+            restart()
         step()
     eng.sync()
     eng.kernel_ms()                       # drop warm-up launches from the event accumulator
@@ -276,7 +339,9 @@ def run(args, emit=True):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for g in range(args.warmup, args.warmup + args.steps):
+        if g and g % per_pass == 0:
+            t0 += restart()               # untimed
         step()
     eng.sync()
     torch.cuda.synchronize()
@@ -287,9 +352,10 @@ def run(args, emit=True):
 
     # chains at the end of a frame have fewer CTUs left than cps: count what was really decided in the timed steps
     timed_ctus_gpu = 0
-    for seed, qp, k in chain_list:
-        n_in_slice = min(sl, n_ctu - k * sl)
-        timed_ctus_gpu += max(0, min(n_in_slice, walked) - min(n_in_slice, args.warmup * cps))
+    slice_lengths = [min(sl, n_ctu - k * sl) for _, _, k in chain_list]
+    for n_in_slice in set(slice_lengths):
+        per_chain = sum(max(0, min(n_in_slice, b) - min(n_in_slice, a)) for a, b in map(span, range(args.warmup, args.warmup + args.steps)))
+        timed_ctus_gpu += slice_lengths.count(n_in_slice) * per_chain
     if dist is not None:
         t = torch.tensor([timed_ctus_gpu], dtype=torch.float64, device=None if rehearsal else dev)
         dist.all_reduce(t)
@@ -308,6 +374,12 @@ def run(args, emit=True):
                 dist.broadcast(buf, src=owner)
                 if rank == 0 and owner != 0:
                     v[a:b] = buf.to(dev)
+
+    if rank == 0 and args.dump_outputs:
+        a, b = span(args.warmup + args.steps - 1)
+        last = [(ci, k * sl + c) for ci, (seed, qp, k) in enumerate(chain_list) for c in range(a, min(b, n_ctu - k * sl, sl))]
+        # ranks other than 0 keep the reconstruction of the slices they own
+        dump_outputs(args.dump_outputs, pkg, torch, np, chain_list, last, outs, None if strong else recs, W, H)
 
     if rank == 0:
         per_launch = timed_ctus_gpu / max(1, args.steps)
@@ -328,8 +400,10 @@ def run(args, emit=True):
             "config": {"workload": what + f"; {len(seeds)} {'clips' if ldp else 'frames'} x {len(qps)} QP x {len(my_slices)} slices of {sl} CTUs (HM SliceMode 1) = {n_chains} chains/GPU, "
                                           f"{cps} CTUs/chain/step, lowest QP first",
                        "chains_per_gpu": n_chains, "ctus_per_step": int(per_launch) * (1 if strong else world),
-                       "timed_ctu_range": f"CTUs {args.warmup * cps}..{walked - 1} of every {sl}-CTU slice: first-row CTUs (no above neighbour), second-row CTUs "
-                                          f"(above / above-right neighbours) and, in the last slice of a frame, the partial bottom CTU row",
+                       "timed_ctu_range": (f"CTUs {args.warmup * cps}..{walked - 1} of every {sl}-CTU slice: first-row CTUs (no above neighbour), second-row CTUs "
+                                           f"(above / above-right neighbours) and, in the last slice of a frame, the partial bottom CTU row") if walked <= sl else
+                                          (f"{args.steps} steps of {cps} CTUs over every {sl}-CTU slice, each chain starting its slice again after "
+                                           f"{per_pass} steps (untimed); warm-up {args.warmup} steps"),
                        **({"rehearsal": "all ranks on one GPU over gloo: not a scaling measurement"} if rehearsal else {}),
                        **({"shard": "slices of the same frames over the ranks; outputs gathered on rank 0 after the timed region"} if strong else {}),
                        "state": args.state if switches is None else
@@ -349,7 +423,7 @@ def run(args, emit=True):
                                  "passes of this bench, times the CTUs of a launch); `valu_issue_frac` = VALU wave instructions retired per second over 256 CUs x 4 SIMDs x 2.4 GHz / 2: DESIGN.md 3"},
         }
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             import hmo_py
             qp_list = [32] if ldp else qps
             legs = []
@@ -376,7 +450,7 @@ def run(args, emit=True):
                                                "the oracle's PU/TU search loops are pinned by the reference's own TEncSearch.cpp, its CU-level glue (xCompressCU) is restated"}
         else:
             res["cpu_baseline"] = None
-        if world == 1 and not args.no_sweep:
+        if world == 1 and args.full and not args.no_sweep:
             # (b) transfers the metric's definition puts next to the decision: source planes in, fcu_ctu_out out (pinned host memory)
             nf = min(8, len(seeds))
             host = [torch.empty((nf,) + tuple(p.shape), dtype=torch.uint8).pin_memory() for p in frames[seeds[0]]]
@@ -444,10 +518,10 @@ def run(args, emit=True):
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if args.config != "intra" or world > 1 or args.no_ldp_leg or args.state != "training":
+    if not args.full or args.config != "intra" or world > 1 or args.no_ldp_leg or args.state != "training":
         run(args)
         return
-    # the default command (the driver's): the intra measurement is the JSON line; a short lowdelay_P measurement (BASELINE
+    # the default command with --full: the intra measurement is the JSON line; a short lowdelay_P measurement (BASELINE
     # configs[4], the shape of `--config ldp`: 240 clips x 17 slices, TZ search, AMP off, fewer steps) rides under "ldp"
     res = run(args, emit=False)
     a2 = parse_args(["--config", "ldp", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sweep"])

@@ -1,6 +1,6 @@
 """Bandwidth of the two OBF pre-pass kernels on a batch of 4K luma planes (run on the GPU box)."""
 import os, sys, json
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
 pkg = g.load_package()
 import torch

@@ -1,5 +1,5 @@
 import sys, os, ctypes as C, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT','/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
 pkg = g.load_package()
 import torch
