@@ -267,6 +267,13 @@ struct Chain {
   const uint8_t *refs[FCU_MAX_REF][3];
   int n_ref, poc, ref_poc[FCU_MAX_REF], col_poc, col_ref_poc[FCU_MAX_REF];
   int int_mv_r[FCU_MAX_REF][2];
+  /* WaveFrontSynchro row chain (fcu_wpp_begin), written by the host only: wpp = 1 binds the chain to one CTU row of a one-slice
+   * I picture, wpp_above = chain index of the row above (-1 for row 0), wpp_sync_in / wpp_sync_out = the sync slots (NCTX
+   * context bytes, m_entropyCodingSyncContextState) of the row above / of this row.  The slots themselves are device memory
+   * of the context (fcu_kernels.hip), not part of the descriptor: no host copy of the descriptor ever overwrites them. */
+  int wpp, wpp_above;
+  const uint8_t *wpp_sync_in;
+  uint8_t *wpp_sync_out;
 };
 enum { DEC_TRAINING = 0, DEC_VERIFYING = 1, DEC_TESTING = 2 };
 
@@ -3335,7 +3342,12 @@ FCU_DEV void load_hot_tables()
   }
 }
 
-/* ---- one CTU of one chain: the loop body of TEncSlice::compressSlice, TEncSlice.cpp:1380-1551 */
+/* ---- one CTU of one chain: the loop body of TEncSlice::compressSlice, TEncSlice.cpp:1380-1551.
+ * WPP = a WaveFrontSynchro row chain (Chain::wpp): the first CTU of a row below the first restarts the coder (resetEntropy) and,
+ * when the picture is at least two CTUs wide, takes the contexts saved after the second CTU of the row above (loadContexts of
+ * m_entropyCodingSyncContextState, TEncSlice.cpp:1396-1411: contexts only, the Q15 counter stays as the reset leaves it); after
+ * the second CTU of its own row it saves its contexts for the row below (:1514-1517).  WPP = false is the plain chain. */
+template <bool WPP = false>
 FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
 {
   C = FCU_UNI(C); G = FCU_UNI(G); ctuRsAddr = FCU_UNI(ctuRsAddr);
@@ -3348,7 +3360,13 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
   E.cur_ctu = ctuRsAddr; E.slice_start = sliceStart;
   fcu_ctu_out *out = &C->out[ctuRsAddr];
   const int x = (ctuRsAddr % C->w_ctu) * CTU, y = (ctuRsAddr / C->w_ctu) * CTU;
-  FCU_SERIAL { g_S.env = E; if (ctuRsAddr == sliceStart) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
+  const int col = ctuRsAddr % C->w_ctu;
+  const bool row_start = WPP && col == 0 && ctuRsAddr != sliceStart;
+  FCU_SERIAL { g_S.env = E; if (ctuRsAddr == sliceStart || row_start) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
+  if (row_start && C->w_ctu >= 2) {
+    const uint8_t *src = C->wpp_sync_in;
+    FCU_FOR_LANES { Cabac *d = slot_ptr(E, 0, CI_CURR_BEST); for (int i = lane; i < NCTX; i += 64) d->ctx[i] = src[i]; }   /* lane-indexed: vector loads */
+  }
   FCU_FOR_LANES {                                            /* TComDataCU::initCtu defaults, TComDataCU.cpp:474-560 */
     for (int i = lane; i < NPART; i += 64) {
       out->depth[i] = 0; out->width[i] = CTU; out->height[i] = CTU; out->skip[i] = 0; out->part_size[i] = SIZE_NONE; out->pred_mode[i] = MODE_NONE;
@@ -3379,8 +3397,78 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
       cab_copy1(&C->state, &g_S.cab[CAB_GOON]);
     }
     FCU_TOC(E, t9_, 9);
+    if (WPP && col == 1) {
+      uint8_t *dst = C->wpp_sync_out;
+      FCU_FOR_LANES { for (int i = lane; i < NCTX; i += 64) dst[i] = g_S.cab[CAB_GOON].ctx[i]; }
+    }
   }
   FCU_TOC(E, t10_, 10);
+}
+
+/* ---- WaveFrontSynchro: one CTU row of a one-slice I picture as a chain (TEncSlice.cpp:1386-1411,1514-1517) ---------------
+ * Row r may decide CTU x once row r-1 has finished CTU min(x + 1, W - 1): that completes every neighbour CTU x reads (left,
+ * above-left, above, above-right) and, for x == 0, the sync slot written after CTU 1 of the row above.  The rows of a picture
+ * hand these bytes (fcu_ctu_out entries, reconstruction rows, the sync slot) over through per-chain progress words:
+ * ctl[WPP_CTL_WORDS + chain] = CTUs the chain has finished in this launch; ctl[0] = ticket counter, ctl[1] = abort word. */
+enum { WPP_CTL_WORDS = 4, WPP_SYNC_BYTES = 192 };          /* sync slot: NCTX context bytes, padded */
+#ifdef FCU_EMU
+/* the emulator runs the chains one after the other in index order (row above first): a wait is a claim that holds already */
+FCU_DEV bool wpp_wait(unsigned *ctl, int above, unsigned need) { FCU_CHECK(ctl[WPP_CTL_WORDS + above] >= need); return true; }
+FCU_DEV void wpp_publish(unsigned *ctl, int chain, unsigned done) { ctl[WPP_CTL_WORDS + chain] = done; }
+#else
+/* 120 s of s_memrealtime (100 MHz): far beyond the longest wait of a healthy launch (a row waits at most for the rows above it to
+ * advance two CTUs each) */
+#define FCU_WPP_GIVE_UP_TICKS (120ull * 100000000ull)
+/* consumer (cdna_hip_programming.md 6, Guideline 16): lane 0 polls the producer's word relaxed at agent scope, the value is made
+ * wave-uniform, s_sleep between polls; ONE agent-scope acquire after the match, then plain (vector) loads.  Gives up -- and
+ * raises the abort word that stops every other waiter -- after FCU_WPP_GIVE_UP_TICKS or when another wave has aborted. */
+FCU_DEV bool wpp_wait(unsigned *ctl_, int above, unsigned need)
+{
+  FCU_HBM unsigned *ctl = (FCU_HBM unsigned *)ctl_;
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  for (;;) {
+    unsigned v = 0, ab = 0;
+    if (threadIdx.x == 0) {
+      v = __hip_atomic_load(ctl + WPP_CTL_WORDS + above, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ab = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    v = (unsigned)__builtin_amdgcn_readfirstlane((int)v); ab = (unsigned)__builtin_amdgcn_readfirstlane((int)ab);
+    if (ab != 0) return false;
+    if (v >= need) break;
+    if (__builtin_amdgcn_s_memrealtime() - t0 > FCU_WPP_GIVE_UP_TICKS) {
+      if (threadIdx.x == 0) __hip_atomic_store(ctl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(8);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return true;
+}
+/* producer: drain this wave's stores of the CTU (its fcu_ctu_out entry, reconstruction, sync slot), agent-scope release, drain
+ * again (the fence's own wait may be dropped: Guideline 16 Pitfall 12), then lane 0 stores the progress word atomically */
+FCU_DEV void wpp_publish(unsigned *ctl_, int chain, unsigned done)
+{
+  FCU_HBM unsigned *ctl = (FCU_HBM unsigned *)ctl_;
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (threadIdx.x == 0) __hip_atomic_store(ctl + WPP_CTL_WORDS + chain, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+/* one WPP row chain (`chain` = its index, the one its progress word is kept under) decided to the end of its row; 0 = gave up */
+FCU_DEV FCU_NOINLINE int run_wpp_chain(Chain *C, Scratch *G, unsigned *ctl, int chain)
+{
+  C = FCU_UNI(C); G = FCU_UNI(G); ctl = FCU_UNI(ctl); chain = FCU_UNI(chain);
+  load_hot_tables();
+  const int above = FCU_UNI(C->wpp_above), W = FCU_UNI(C->w_ctu), end = FCU_UNI(C->end_ctu);
+  for (int a = FCU_UNI(C->next_ctu); a < end; a++) {
+    const int x = a % W;
+    if (above >= 0 && !wpp_wait(ctl, above, (unsigned)(x + 2 < W ? x + 2 : W))) return 0;
+    compress_ctu<true>(C, G, a);
+    FCU_SERIAL { C->next_ctu = a + 1; }
+    wpp_publish(ctl, chain, (unsigned)(x + 1));
+  }
+  return 1;
 }
 
 } // namespace fcu

@@ -40,6 +40,19 @@ fcu_ctu_engine(Chain *chains, Scratch *scratch, int first, int ctus)
   run_chain(&chains[first + blockIdx.x], &scratch[first + blockIdx.x], ctus);
 }
 
+/* WaveFrontSynchro: the row chains [first, first + gridDim.x) of whole pictures, one launch.  A wave takes a ticket and decides
+ * chain first + ticket: the rows of a picture are bound top to bottom at increasing chain indices, so the chain a wave waits on
+ * holds an earlier ticket and is already running (or done) -- no deadlock whatever the dispatch order, and the launch may hold
+ * more chains than are resident.  ctl: fcu_ctx::d_wpp_ctl, zeroed before every launch. */
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FCU_WAVES_PER_EU, FCU_WAVES_PER_EU)))
+fcu_ctu_engine_wpp(Chain *chains, Scratch *scratch, unsigned *ctl, int first)
+{
+  unsigned t = 0;
+  if (threadIdx.x == 0) t = __hip_atomic_fetch_add((FCU_HBM unsigned *)ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int i = first + __builtin_amdgcn_readfirstlane((int)t);
+  run_wpp_chain(&chains[i], &scratch[i], ctl, i);
+}
+
 /* Reference picture padding (TComPicYuv::extendPicBorder): every thread writes 16 consecutive bytes of one row of a
  * padded plane; the source coordinate is clamped into the picture.  HBM-bound: reads W*H*1.5, writes (W+160)*(H+160)*1.5/.. */
 __global__ void __launch_bounds__(256) fcu_pad_plane(const uint8_t *src, int w, int h, uint8_t *dst, int margin)
@@ -71,6 +84,10 @@ struct fcu_ctx {
   unsigned *d_hist; size_t hist_cap; int *d_thr; size_t thr_cap;
   /* persistent scratch of fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
   void *d_sao; size_t sao_cap;
+  /* WaveFrontSynchro (allocated by the first fcu_wpp_begin): d_wpp_ctl = the words a launch polls (ticket, abort, one progress
+   * word per chain), a block of its own from the allocation's start, wpp_ctl_bytes a multiple of 16, zeroed before every launch;
+   * d_wpp_sync = one sync slot of WPP_SYNC_BYTES per chain */
+  unsigned *d_wpp_ctl; size_t wpp_ctl_bytes; uint8_t *d_wpp_sync;
 };
 
 /* Launch timing keeps two events per launch until they are read.  A long-running caller that never asks for
@@ -136,6 +153,7 @@ int fcu_create(const fcu_seq_params *sp, fcu_ctx **out)
   c->sp = *sp; c->n_ctu = ((sp->width + 63) / 64) * ((sp->height + 63) / 64);
   c->ms_acc = 0; c->launches = 0;
   c->d_chains = nullptr; c->d_scratch = nullptr; c->d_hist = nullptr; c->hist_cap = 0; c->d_thr = nullptr; c->thr_cap = 0; c->d_sao = nullptr; c->sao_cap = 0;
+  c->d_wpp_ctl = nullptr; c->wpp_ctl_bytes = 0; c->d_wpp_sync = nullptr;
   struct Guard { fcu_ctx *c; ~Guard() { if (c) { hipFree(c->d_chains); hipFree(c->d_scratch); delete c; } } } guard{ c };   /* frees on every early return */
   HIPCHK(hipMalloc((void **)&c->d_chains, sizeof(Chain) * (size_t)sp->max_chains));
   HIPCHK(hipMalloc((void **)&c->d_scratch, sizeof(Scratch) * (size_t)sp->max_chains));
@@ -155,6 +173,7 @@ void fcu_destroy(fcu_ctx *c)
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
   hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->d_hist); hipFree(c->d_thr); hipFree(c->d_sao);
+  hipFree(c->d_wpp_ctl); hipFree(c->d_wpp_sync);
   delete c;
 }
 
@@ -282,6 +301,7 @@ int fcu_chain_set_range(fcu_ctx *c, int chain, int first_ctu, int n_ctus)
   if (!c || chain < 0 || chain >= c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_chain_set_range: bad argument");
   Chain &h = c->h_chains[(size_t)chain];
   if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_range: chain not bound (fcu_chain_begin)");
+  if (h.wpp) return fail(FCU_ERR_STATE, "fcu_chain_set_range: a WaveFrontSynchro row chain keeps the row fcu_wpp_begin gave it");
   const int sl = h.p.slice_ctus;
   if (first_ctu < 0 || n_ctus <= 0 || first_ctu + n_ctus > h.n_ctu) return fail(FCU_ERR_ARG, "fcu_chain_set_range: range outside the frame");
   /* a chain may only start where the reference resets its entropy coder and cuts the neighbourhood: at a slice start */
@@ -302,6 +322,7 @@ int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream
   if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains || ctus <= 0) return fail(FCU_ERR_ARG, "fcu_compress_chains: bad range");
   for (int i = first; i < first + n; i++) {
     if (c->h_chains[(size_t)i].out == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_chains: chain not bound (fcu_chain_begin)");
+    if (c->h_chains[(size_t)i].wpp) return fail(FCU_ERR_STATE, "fcu_compress_chains: a WaveFrontSynchro row chain is decided by fcu_compress_wpp");
     if (c->h_chains[(size_t)i].p.slice_type == SLICE_P && c->h_chains[(size_t)i].ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_chains: P chain without reference picture (fcu_chain_set_reference)");
   }
   HIPCHK(hipSetDevice(c->sp.device));
@@ -315,6 +336,72 @@ int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream
   c->ev.push_back(e0); c->ev.push_back(e1);
   harvest_events(c, FCU_MAX_PENDING_EVENTS);
   for (int i = first; i < first + n; i++) { int &p = c->h_pos[(size_t)i]; p += ctus; if (p > c->h_chains[(size_t)i].end_ctu) p = c->h_chains[(size_t)i].end_ctu; }
+  return FCU_OK;
+}
+
+int fcu_wpp_rows(const fcu_ctx *c) { return c ? (c->sp.height + 63) / 64 : 0; }
+
+int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
+                  const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin: bad argument");
+  if (fp->slice_type != FCU_SLICE_I) return fail(FCU_ERR_ARG, "fcu_wpp_begin: WaveFrontSynchro is built for I slices only (a P slice carries m_integerMv2Nx2N from the last CTU of the row above, TEncSearch.cpp:3833-3842)");
+  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, "fcu_wpp_begin: WaveFrontSynchro needs one slice per picture (slice_ctus 0)");
+  const int rows = fcu_wpp_rows(c), W = (c->sp.width + 63) / 64;
+  if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_wpp_begin: too few chains for one chain per CTU row (fcu_wpp_rows)");
+  if (!c->d_wpp_ctl) {
+    const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
+    HIPCHK(hipSetDevice(c->sp.device));
+    HIPCHK(hipMalloc((void **)&c->d_wpp_ctl, ctl));
+    if (hipMalloc((void **)&c->d_wpp_sync, (size_t)WPP_SYNC_BYTES * c->sp.max_chains) != hipSuccess) {
+      hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, "fcu_wpp_begin: out of device memory");
+    }
+    c->wpp_ctl_bytes = ctl;
+  }
+  const int rc = fcu_chain_begin(c, first_chain, fp, oy, ou, ov, ry, ru, rv, dev_out);     /* checks the rest, fills the row-0 descriptor */
+  if (rc != FCU_OK) return rc;
+  const Chain base = c->h_chains[(size_t)first_chain];
+  for (int r = 0; r < rows; r++) {
+    Chain &h = c->h_chains[(size_t)(first_chain + r)];
+    h = base;
+    h.next_ctu = r * W; h.end_ctu = (r + 1) * W;
+    h.wpp = 1; h.wpp_above = r ? first_chain + r - 1 : -1;
+    h.wpp_sync_in = r ? c->d_wpp_sync + (size_t)WPP_SYNC_BYTES * (first_chain + r - 1) : nullptr;
+    h.wpp_sync_out = c->d_wpp_sync + (size_t)WPP_SYNC_BYTES * (first_chain + r);
+    c->h_pos[(size_t)(first_chain + r)] = r * W;
+  }
+  HIPCHK(hipMemcpy(&c->d_chains[first_chain], &c->h_chains[(size_t)first_chain], sizeof(Chain) * (size_t)rows, hipMemcpyHostToDevice));
+  return FCU_OK;
+}
+
+int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
+{
+  if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
+  for (int i = first; i < first + n; i++) {
+    const Chain &h = c->h_chains[(size_t)i];
+    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin");
+    /* a picture starts with its row 0 (at `first` or right after the last row of the picture before it) and its rows follow */
+    const bool starts_ok = h.wpp_above < 0 ? (i == first || c->h_chains[(size_t)i - 1].end_ctu == c->h_chains[(size_t)i - 1].n_ctu) : (i > first && h.wpp_above == i - 1);
+    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin");
+    if (i == first + n - 1 && h.end_ctu != h.n_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture");
+    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin)");
+  }
+  HIPCHK(hipSetDevice(c->sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  HIPCHK(hipMemsetAsync(c->d_wpp_ctl, 0, c->wpp_ctl_bytes, st));          /* ticket, abort and progress words: every launch */
+  HIPCHK(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(fcu_ctu_engine_wpp, dim3((unsigned)n), dim3(64), 0, st, c->d_chains, c->d_scratch, c->d_wpp_ctl, first);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e1, st));
+  c->ev.push_back(e0); c->ev.push_back(e1);
+  harvest_events(c, FCU_MAX_PENDING_EVENTS);
+  unsigned abort_word = 0;
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(&abort_word, c->d_wpp_ctl + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (abort_word) return fail(FCU_ERR_STATE, "fcu_compress_wpp: a row waited for the row above beyond the give-up time; the launch was abandoned");
+  for (int i = first; i < first + n; i++) c->h_pos[(size_t)i] = c->h_chains[(size_t)i].end_ctu;
   return FCU_OK;
 }
 

@@ -86,7 +86,8 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_chain_set_decision", "fcu_get_verify_counts", "fcu_decision_switch", "fcu_frame_state", "fcu_deblock",
            "fcu_build_info", "fcu_abi_sizeof", "fcu_tcm_threshold", "fcu_chain_set_reference", "fcu_pad_reference", "fcu_pad_sizes", "fcu_ldp_slice", "fcu_get_ctx_state_full",
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
-           "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state"]
+           "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
+           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -164,6 +165,9 @@ def load_lib():
     lib.fcu_chain_set_collocated_pocs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.fcu_chain_get_search_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     lib.fcu_chain_set_search_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    lib.fcu_wpp_rows.argtypes = [C.c_void_p]
+    lib.fcu_wpp_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
+    lib.fcu_compress_wpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -353,6 +357,36 @@ class CuEngine:
             first = k * slice_ctus
             self.set_range(first_chain + k, first, min(slice_ctus, self.n_ctu - first))
         return n_sl, rec, out
+
+    def init_wpp_picture(self, first_chain, org, qp, rec=None, out=None, **flags):
+        """One picture, one slice, WaveFrontSynchro on (fcu_wpp_begin): chains [first_chain, first_chain + n_rows) become its
+        CTU rows, top to bottom; they share the picture's planes and fcu_ctu_out array.  flags: fcu_frame_params fields of an
+        I slice.  Returns (n_rows, rec, out)."""
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
+        if rec is None:
+            rec = [torch.zeros_like(p) for p in planes]
+        if out is None:
+            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
+        fp = FrameParams()
+        self.lib.fcu_default_frame_params(C.byref(fp), qp)
+        known = {n for n, _ in FrameParams._fields_}
+        for k, v in flags.items():
+            if k not in known:
+                raise TypeError(f"init_wpp_picture: unknown frame parameter {k!r}")
+            setattr(fp, k, v)
+        self._chk(self.lib.fcu_wpp_begin(self.h, first_chain, C.byref(fp), *[p.data_ptr() for p in planes],
+                                         *[p.data_ptr() for p in rec], out.data_ptr()), "fcu_wpp_begin")
+        n_rows = self.lib.fcu_wpp_rows(self.h)
+        for r in range(n_rows):
+            self._keep[first_chain + r] = (planes, rec, out)
+        return n_rows, rec, out
+
+    def compress_wpp(self, first, n, stream=None):
+        """decides the WPP row chains [first, first + n) (whole pictures) to the end in one launch; returns once it has finished"""
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_compress_wpp(self.h, first, n, s), "fcu_compress_wpp")
 
     def set_range(self, chain, first_ctu, n_ctus):
         self._chk(self.lib.fcu_chain_set_range(self.h, chain, first_ctu, n_ctus), "fcu_chain_set_range")

@@ -78,11 +78,16 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
-        run as concurrent chains, but every slice start cuts the intra neighbourhood and resets CABAC."""
+        run as concurrent chains, but every slice start cuts the intra neighbourhood and resets CABAC.
+        wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains, each row waiting for the row above
+        (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.  Cannot be combined with slice_ctus."""
+        if wpp and slice_ctus:
+            raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None)")
+        self.wpp = wpp
         self.width, self.height, self.qp, self.fast, self.do_deblock, self.flags = width, height, qp, fast, deblock, flags
         self.in_flight = max(1, in_flight)
         w_ctu = (width + 63) // 64
@@ -90,6 +95,9 @@ class SequenceDecider:
         self.slice_ctus = slice_ctus if slice_ctus else n_ctu
         self.slice_mode = "SliceMode 0 (one slice per picture)" if self.slice_ctus >= n_ctu else f"SliceMode 1, SliceArgument {self.slice_ctus}"
         self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
+        if wpp:
+            self.slice_mode += ", WaveFrontSynchro"
+            self.n_slices = (height + 63) // 64                 # chains per picture: one per CTU row
         self.eng = _engine.CuEngine(width, height, max_chains=self.n_slices * self.in_flight, device=device)
         self.schedule = schedule or FastDecisionSchedule()
         self.poc = 0
@@ -118,13 +126,19 @@ class SequenceDecider:
             poc = self.poc + i
             state, sk, te = self.schedule.begin_picture(poc) if self.fast else (TRAINING, np.zeros(4, np.uint8), np.zeros(4, np.uint8))
             first = i * self.n_slices
-            n_sl, rec, out = eng.init_slice_chains(first, yuv, self.qp, self.slice_ctus, **self.flags)
+            if self.wpp:
+                n_sl, rec, out = eng.init_wpp_picture(first, yuv, self.qp, **self.flags)
+            else:
+                n_sl, rec, out = eng.init_slice_chains(first, yuv, self.qp, self.slice_ctus, **self.flags)
             if state != TRAINING:
                 obf = eng.obf_prepass(eng._keep[first][0][0])[0][0].contiguous()
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
-        eng.compress_chains(0, len(yuvs) * self.n_slices, self.slice_ctus)
+        if self.wpp:
+            eng.compress_wpp(0, len(yuvs) * self.n_slices)
+        else:
+            eng.compress_chains(0, len(yuvs) * self.n_slices, self.slice_ctus)
         nb = _engine.CTU_OUT_BYTES
         for p in pics:
             p["verify"] = eng.verify_counts(p["first"], self.n_slices) if p["state"] == VERIFYING else None

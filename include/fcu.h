@@ -27,6 +27,9 @@
  *   TEncSampleAdaptiveOffset::SAOProcess           fcu_sao (statistics, per-CTU parameter decision, offset pass) +
  *     (TEncSampleAdaptiveOffset.cpp:257,              fcu_sao_enabled / fcu_sao_update_rate (decidePicParams and the
  *      TEncGOP.cpp:1427-1441)                         m_saoDisabledRate bookkeeping across pictures, :363-395,895-917)
+ *   WaveFrontSynchro=1 row loop of                 fcu_wpp_begin (one chain per CTU row of a one-slice I picture),
+ *     TEncSlice::compressSlice                       fcu_compress_wpp (every row of whole pictures in one launch,
+ *     (TEncSlice.cpp:1386-1411,1514-1517)            a row waiting for the row above), fcu_wpp_rows
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -167,6 +170,27 @@ int  fcu_chain_set_range(fcu_ctx *c, int chain, int first_ctu, int n_ctus);
 /* Advance chains [first, first+n) by up to `ctus` CTUs each (raster order; compressCtu +
  * encodeCtu replay per CTU).  Asynchronous on `hip_stream` (hipStream_t or NULL). */
 int  fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream);
+/* ---- WaveFrontSynchro (WPP, entropy_coding_sync_enabled_flag; TEncSlice.cpp:1386-1411,1514-1517): the picture stays ONE
+ * slice, so every earlier CTU stays available as a neighbour, and each CTU row restarts its contexts (resetEntropy) from the
+ * state saved after the second CTU of the row above (contexts only; a one-CTU-wide picture keeps the plain reset).  Row r may
+ * decide CTU x once row r-1 has finished CTU x+1: a picture of W x H CTUs is H chains with a critical path of W + 2(H-1) CTUs.
+ * fcu_wpp_begin binds chains [first_chain, first_chain + fcu_wpp_rows(c)) to the CTU rows of ONE picture, top to bottom (the
+ * arguments of fcu_chain_begin; the rows share the planes and dev_out).  Built for I slices with one slice per picture:
+ * fp->slice_type must be FCU_SLICE_I and fp->slice_ctus 0, else FCU_ERR_ARG -- P slices (HM carries m_integerMv2Nx2N from the
+ * LAST CTU of the row above into a row, TEncSearch.cpp:3833-3842, a state a wavefront does not have yet) and WPP with SliceMode 1
+ * are not supported; neither is writing substreams / entry points.  Too few chains: FCU_ERR_ARG.
+ * fcu_chain_set_decision, fcu_chain_set_pu_trace, fcu_get_verify_counts (rows added up in chain order), fcu_chain_position and
+ * fcu_get_ctx_state (the state after the chain's row) work on row chains as on slice chains; fcu_compress_chains /
+ * fcu_compress_ctu / fcu_chain_set_range on a row chain return FCU_ERR_STATE. */
+int  fcu_wpp_rows(const fcu_ctx *c);
+int  fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
+                   const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
+                   uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
+/* Decide every row chain in [first, first + n) to the end, in one launch on `hip_stream`.  The range must hold whole pictures
+ * bound by fcu_wpp_begin and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin).  It may hold more
+ * chains than the GPU keeps resident.  Returns when the launch has finished; FCU_ERR_STATE if a row gave up waiting for the
+ * row above (a bounded wait of 120 s; the pictures of the launch are then undefined). */
+int  fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream);
 /* HM-shaped call: decide CTU `ctuRsAddr` (must be the chain's next CTU) and copy its
  * TComDataCU arrays to host memory.  Synchronous. */
 int  fcu_compress_ctu(fcu_ctx *c, int chain, uint32_t ctuRsAddr, fcu_ctu_out *host_out);

@@ -11,7 +11,9 @@ encoder_intra_main.cfg` that this repository replaces (no bitstream is written).
 Slices: by default a picture is ONE slice, as in the reference's configuration (SliceMode 0) -- pictures side by side
 (--in-flight) are then the source of parallelism.  --slice-ctus N / --row-slices select HM's SliceMode 1 with N CTUs (one
 CTU row) per slice: a different encoder configuration (neighbourhood cut and CABAC reset at every slice start), whose
-slices are decided concurrently.  The slice mode is echoed on every picture line.
+slices are decided concurrently.  --wpp keeps one slice per picture and switches WaveFrontSynchro on (HM's WaveFrontSynchro=1):
+the CTU rows of a picture are decided concurrently, each row starting from the contexts the row above had after its second CTU
+and waiting for the row above to stay two CTUs ahead.  The slice mode is echoed on every picture line.
 """
 import argparse
 import os
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--in-flight", type=int, default=16, help="pictures decided side by side when the schedule allows it")
     ap.add_argument("--slice-ctus", type=int, default=0, help="SliceMode 1: CTUs per slice (default: one slice per picture)")
     ap.add_argument("--row-slices", action="store_true", help="SliceMode 1 with one CTU row per slice")
+    ap.add_argument("--wpp", action="store_true", help="WaveFrontSynchro: one slice per picture, its CTU rows decided as chains that wait for the row above")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
@@ -47,7 +50,7 @@ def main():
     pkg = g.load_package()
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
-    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight,
+    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp,
                               schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
