@@ -267,13 +267,18 @@ struct Chain {
   const uint8_t *refs[FCU_MAX_REF][3];
   int n_ref, poc, ref_poc[FCU_MAX_REF], col_poc, col_ref_poc[FCU_MAX_REF];
   int int_mv_r[FCU_MAX_REF][2];
-  /* WaveFrontSynchro row chain (fcu_wpp_begin), written by the host only: wpp = 1 binds the chain to one CTU row of a one-slice
-   * I picture, wpp_above = chain index of the row above (-1 for row 0), wpp_sync_in / wpp_sync_out = the sync slots (NCTX
-   * context bytes, m_entropyCodingSyncContextState) of the row above / of this row.  The slots themselves are device memory
-   * of the context (fcu_kernels.hip), not part of the descriptor: no host copy of the descriptor ever overwrites them. */
+  /* WaveFrontSynchro row chain (fcu_wpp_begin / fcu_wpp_begin_p), written by the host only: wpp = 1 binds the chain to one CTU
+   * row of a one-slice picture, wpp_above = chain index of the row above (-1 for row 0), wpp_sync_in / wpp_sync_out = the sync
+   * slots (NCTX context bytes, m_entropyCodingSyncContextState) of the row above / of this row.  The slots themselves are device
+   * memory of the context (fcu_kernels.hip), not part of the descriptor: no host copy of the descriptor ever overwrites them. */
   int wpp, wpp_above;
   const uint8_t *wpp_sync_in;
   uint8_t *wpp_sync_out;
+#ifdef FCU_EMU
+  /* emulator only (the GPU layout has neither): bit r of wpp_mv_known = int_mv_r[r] holds HM's value (written by this row's
+   * search, or taken from the caller / the row above); wpp_mv_rbw counts TZ searches that read a slot before it was known */
+  int wpp_mv_known, wpp_mv_rbw;
+#endif
 };
 enum { DEC_TRAINING = 0, DEC_VERIFYING = 1, DEC_TESTING = 2 };
 
@@ -3455,17 +3460,55 @@ FCU_DEV void wpp_publish(unsigned *ctl_, int chain, unsigned done)
   if (threadIdx.x == 0) __hip_atomic_store(ctl + WPP_CTL_WORDS + chain, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #endif
+/* ---- P slices: m_integerMv2Nx2N across rows.  HM walks the CTUs of a WPP picture in raster order, so the TZ start vectors
+ * (int_mv_r, TEncSearch.cpp:3833-3842) a row begins with are the ones the row above ended with.  They are read only by a TZ
+ * search that is not the depth-0 2Nx2N one (:3833-3837) and written after every 2Nx2N TZ search (:3839-3842).  A CTU that holds
+ * a 64x64 CU always runs that depth-0 2Nx2N search on every reference index in order first (merge 2Nx2N, then inter 2Nx2N:
+ * TEncCu.cpp:774-780, oracle/hmo_search.c:851-864), so a row whose first CTU is full writes slots [0, n_ref) before it reads
+ * any, and only a row that begins on a boundary CTU (the partial bottom row, a picture narrower than 64) reads what the row
+ * above left.  Hence, under TZ search (slots >= n_ref, and all of them under full search, are never written):
+ *   - a row below the first whose first CTU is a boundary CTU waits for the whole row above and takes all its slots first;
+ *   - every row below the first, at its end, takes from the row above the slots it did not write (rule: the row wrote
+ *     [0, n_ref) iff TZ search and a full first CTU; a boundary-first row already holds every slot), so each row chain ends
+ *     with HM's state after its row, the last one with HM's state after the picture.
+ * The row above is finished when either copy happens (progress W, waited for before the first / the last CTU); its own end copy
+ * precedes its last publish.  Lane-indexed loads (vector memory, never the scalar cache: Guideline 16 Pitfall 6). */
+FCU_DEV void wpp_take_search_state(Chain *C, const Chain *A, int first, int end)
+{
+  FCU_FOR_LANES {
+    if (lane >= 2 * first && lane < 2 * end) {
+      const int v = ((const FCU_HBM int *)&A->int_mv_r[0][0])[lane];
+      ((FCU_HBM int *)&C->int_mv_r[0][0])[lane] = v;
+    }
+  }
+#ifdef FCU_EMU
+  C->wpp_mv_known |= ((1 << end) - 1) & ~((1 << first) - 1);
+#endif
+}
 /* one WPP row chain (`chain` = its index, the one its progress word is kept under) decided to the end of its row; 0 = gave up */
 FCU_DEV FCU_NOINLINE int run_wpp_chain(Chain *C, Scratch *G, unsigned *ctl, int chain)
 {
   C = FCU_UNI(C); G = FCU_UNI(G); ctl = FCU_UNI(ctl); chain = FCU_UNI(chain);
   load_hot_tables();
   const int above = FCU_UNI(C->wpp_above), W = FCU_UNI(C->w_ctu), end = FCU_UNI(C->end_ctu);
-  for (int a = FCU_UNI(C->next_ctu); a < end; a++) {
+  const int first = FCU_UNI(C->next_ctu);
+  /* P row below the first: the row above's descriptor (rows of a picture are consecutive chains) and the hand-off rule above */
+  const bool inherit = above >= 0 && C->p.slice_type == SLICE_P;
+  const Chain *A = C + (above - chain);
+  const bool tz = C->p.fast_search != 0, full_first = C->p.width >= CTU && (first / W + 1) * CTU <= C->p.height;
+#ifdef FCU_EMU
+  if (above >= 0) C->wpp_mv_known = 0;
+#endif
+  if (inherit && tz && !full_first && first < end) {
+    if (!wpp_wait(ctl, above, (unsigned)W)) return 0;
+    wpp_take_search_state(C, A, 0, FCU_MAX_REF);
+  }
+  for (int a = first; a < end; a++) {
     const int x = a % W;
     if (above >= 0 && !wpp_wait(ctl, above, (unsigned)(x + 2 < W ? x + 2 : W))) return 0;
     compress_ctu<true>(C, G, a);
     FCU_SERIAL { C->next_ctu = a + 1; }
+    if (inherit && a + 1 == end && (!tz || full_first)) wpp_take_search_state(C, A, tz ? FCU_UNI(C->n_ref) : 0, FCU_MAX_REF);
     wpp_publish(ctl, chain, (unsigned)(x + 1));
   }
   return 1;

@@ -521,9 +521,15 @@ FCU_DEV FCU_NOINLINE void motion_estimation(const CuObj *cu, int ps, int pu, int
   if (P.fast_search) {                                       /* xPatternSearchFast -> xTZSearch; m_integerMv2Nx2N, TEncSearch.cpp:3822-3833 */
     TzCtx t; t.org = org; t.ref0 = ref0; t.rs = rs; t.px = px; t.py = py; t.w = g.w; t.h = g.h; t.step = step; t.predx = predx; t.predy = predy;
     const int usePred = ps != SIZE_2Nx2N || cu->depth_cu != 0;
+#ifdef FCU_EMU
+    if (E.C->wpp && usePred && !((E.C->wpp_mv_known >> refIdx) & 1)) E.C->wpp_mv_rbw++;     /* run_wpp_chain's hand-off rule broken */
+#endif
     tz_search(P, cu, t, ltx, lty, rbx, rby, usePred, FCU_UNI(E.C->int_mv_r[refIdx][0]), FCU_UNI(E.C->int_mv_r[refIdx][1]));
     bx = FCU_UNI(g_S.tz_bx); by = FCU_UNI(g_S.tz_by);
     if (ps == SIZE_2Nx2N) FCU_SERIAL { E.C->int_mv_r[refIdx][0] = bx; E.C->int_mv_r[refIdx][1] = by; }
+#ifdef FCU_EMU
+    if (ps == SIZE_2Nx2N) E.C->wpp_mv_known |= 1 << refIdx;
+#endif
   } else {
   FCU_SERIAL g_S.me_best = ~0ull;
   FCU_FOR_LANES {                                            /* one candidate position per lane */

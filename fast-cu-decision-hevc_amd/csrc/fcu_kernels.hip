@@ -13,6 +13,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 #include <vector>
 #include "fcu_host.h"
 #include "fcu_obf.h"
@@ -108,6 +109,7 @@ static void harvest_events(fcu_ctx *c, size_t keep_pairs)
 /* one buffer per host thread: a failure text never races with another thread's call */
 static thread_local char g_err[256] = "";
 static int fail(int code, const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return code; }
+static int fail(int code, const std::string &msg) { return fail(code, msg.c_str()); }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: %s", #x, hipGetErrorString(e_)); return FCU_ERR_HIP; } } while (0)
 
 extern "C" {
@@ -341,20 +343,19 @@ int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream
 
 int fcu_wpp_rows(const fcu_ctx *c) { return c ? (c->sp.height + 63) / 64 : 0; }
 
-int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
-                  const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+/* the binding both WPP entry points share: `name` for the messages, the slice type already checked by the caller */
+static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, const char *name,
+                    const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin: bad argument");
-  if (fp->slice_type != FCU_SLICE_I) return fail(FCU_ERR_ARG, "fcu_wpp_begin: WaveFrontSynchro is built for I slices only (a P slice carries m_integerMv2Nx2N from the last CTU of the row above, TEncSearch.cpp:3833-3842)");
-  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, "fcu_wpp_begin: WaveFrontSynchro needs one slice per picture (slice_ctus 0)");
+  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": WaveFrontSynchro needs one slice per picture (slice_ctus 0)");
   const int rows = fcu_wpp_rows(c), W = (c->sp.width + 63) / 64;
-  if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_wpp_begin: too few chains for one chain per CTU row (fcu_wpp_rows)");
+  if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains for one chain per CTU row (fcu_wpp_rows)");
   if (!c->d_wpp_ctl) {
     const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
     HIPCHK(hipSetDevice(c->sp.device));
     HIPCHK(hipMalloc((void **)&c->d_wpp_ctl, ctl));
     if (hipMalloc((void **)&c->d_wpp_sync, (size_t)WPP_SYNC_BYTES * c->sp.max_chains) != hipSuccess) {
-      hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, "fcu_wpp_begin: out of device memory");
+      hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, std::string(name) + ": out of device memory");
     }
     c->wpp_ctl_bytes = ctl;
   }
@@ -374,6 +375,36 @@ int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
   return FCU_OK;
 }
 
+int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
+                  const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin: bad argument");
+  if (fp->slice_type != FCU_SLICE_I) return fail(FCU_ERR_ARG, "fcu_wpp_begin: binds I slices only (P slices: fcu_wpp_begin_p)");
+  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin", oy, ou, ov, ry, ru, rv, dev_out);
+}
+
+int fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
+                    const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: bad argument");
+  if (fp->slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: binds P slices only (I slices: fcu_wpp_begin)");
+  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_p", oy, ou, ov, ry, ru, rv, dev_out);
+}
+
+/* the rows of a P picture decide one slice: every row must name row 0's reference pictures and collocated field */
+static bool wpp_same_refs(const Chain &a, const Chain &b)
+{
+  if (a.n_ref != b.n_ref || a.poc != b.poc || a.col != b.col || a.col_poc != b.col_poc || a.ref_stride[0] != b.ref_stride[0]) return false;
+  for (int k = 0; k < 3; k++) if (a.ref[k] != b.ref[k]) return false;
+  for (int r = 0; r < FCU_MAX_REF; r++) {
+    if (a.col_ref_poc[r] != b.col_ref_poc[r]) return false;
+    if (r >= a.n_ref) continue;
+    if (a.ref_poc[r] != b.ref_poc[r]) return false;
+    for (int k = 0; k < 3; k++) if (a.refs[r][k] != b.refs[r][k]) return false;
+  }
+  return true;
+}
+
 int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
 {
   if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
@@ -385,6 +416,11 @@ int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
     if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin");
     if (i == first + n - 1 && h.end_ctu != h.n_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture");
     if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin)");
+    if (h.p.slice_type == SLICE_P) {
+      if (h.ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_wpp: P row without reference picture (fcu_chain_set_reference(s) on every row)");
+      const Chain &row0 = c->h_chains[(size_t)(i - (h.next_ctu / h.w_ctu))];
+      if (!wpp_same_refs(h, row0)) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the rows of a P picture name different reference pictures or collocated fields");
+    }
   }
   HIPCHK(hipSetDevice(c->sp.device));
   hipStream_t st = (hipStream_t)hip_stream;

@@ -87,7 +87,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_build_info", "fcu_abi_sizeof", "fcu_tcm_threshold", "fcu_chain_set_reference", "fcu_pad_reference", "fcu_pad_sizes", "fcu_ldp_slice", "fcu_get_ctx_state_full",
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
-           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp"]
+           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -167,6 +167,7 @@ def load_lib():
     lib.fcu_chain_set_search_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     lib.fcu_wpp_rows.argtypes = [C.c_void_p]
     lib.fcu_wpp_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
+    lib.fcu_wpp_begin_p.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
     lib.fcu_compress_wpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
@@ -304,6 +305,11 @@ class CuEngine:
         self._chk(self.lib.fcu_chain_begin(self.h, chain, C.byref(fp), *[p.data_ptr() for p in planes],
                                            *[p.data_ptr() for p in rec], out.data_ptr()), "fcu_chain_begin")
         self._keep[chain] = (planes, rec, out)
+        self._bind_refs(chain, ref, refs, ref_pocs, poc, col_ref_pocs, col)
+        return rec, out
+
+    def _bind_refs(self, chain, ref=None, refs=None, ref_pocs=None, poc=None, col_ref_pocs=None, col=None):
+        """reference pictures and collocated field of a bound chain (init_chain's arguments of the same names)"""
         if ref is not None:
             self._chk(self.lib.fcu_chain_set_reference(self.h, chain, *[p.data_ptr() for p in ref]), "fcu_chain_set_reference")
             self._keep_ref[chain] = ref
@@ -319,7 +325,6 @@ class CuEngine:
             assert col.is_cuda and col.numel() >= self.n_ctu * CTU_OUT_BYTES
             self._chk(self.lib.fcu_chain_set_collocated(self.h, chain, col.data_ptr()), "fcu_chain_set_collocated")
             self._keep_ref[("col", chain)] = col
-        return rec, out
 
     def search_state(self, chain):
         """m_integerMv2Nx2N of the chain: [(x, y)] per reference index (fcu_chain_get_search_state)"""
@@ -358,10 +363,17 @@ class CuEngine:
             self.set_range(first_chain + k, first, min(slice_ctus, self.n_ctu - first))
         return n_sl, rec, out
 
-    def init_wpp_picture(self, first_chain, org, qp, rec=None, out=None, **flags):
-        """One picture, one slice, WaveFrontSynchro on (fcu_wpp_begin): chains [first_chain, first_chain + n_rows) become its
-        CTU rows, top to bottom; they share the picture's planes and fcu_ctu_out array.  flags: fcu_frame_params fields of an
-        I slice.  Returns (n_rows, rec, out)."""
+    def init_wpp_picture(self, first_chain, org, qp, rec=None, out=None, params=None, ref=None, refs=None, ref_pocs=None, poc=None,
+                         col_ref_pocs=None, col=None, search_state=None, **flags):
+        """One picture, one slice, WaveFrontSynchro on: chains [first_chain, first_chain + n_rows) become its CTU rows, top to
+        bottom; they share the picture's planes and fcu_ctu_out array.  params / flags: the frame parameters as init_chain takes
+        them (I-slice defaults for `qp` without params).  An I slice binds with fcu_wpp_begin; a P slice (params.slice_type P)
+        with fcu_wpp_begin_p, and then takes ref or refs / ref_pocs / poc / col_ref_pocs and col (init_chain) on every row and
+        search_state (set_search_state: what the previous picture left; zero when None) on row 0.  set_decision rewrites the
+        search state: a caller that sets decision states passes search_state=None and calls set_search_state(first_chain, ...)
+        after its set_decision calls.  Returns (n_rows, rec, out)."""
+        if refs is not None:
+            assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
         torch = self.torch
         dev = torch.device("cuda", self.device)
         planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
@@ -370,17 +382,25 @@ class CuEngine:
         if out is None:
             out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
         fp = FrameParams()
-        self.lib.fcu_default_frame_params(C.byref(fp), qp)
+        if params is not None:
+            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
+        else:
+            self.lib.fcu_default_frame_params(C.byref(fp), qp)
         known = {n for n, _ in FrameParams._fields_}
         for k, v in flags.items():
             if k not in known:
                 raise TypeError(f"init_wpp_picture: unknown frame parameter {k!r}")
             setattr(fp, k, v)
-        self._chk(self.lib.fcu_wpp_begin(self.h, first_chain, C.byref(fp), *[p.data_ptr() for p in planes],
-                                         *[p.data_ptr() for p in rec], out.data_ptr()), "fcu_wpp_begin")
+        p_slice = fp.slice_type == SLICE_P
+        begin, name = (self.lib.fcu_wpp_begin_p, "fcu_wpp_begin_p") if p_slice else (self.lib.fcu_wpp_begin, "fcu_wpp_begin")
+        self._chk(begin(self.h, first_chain, C.byref(fp), *[p.data_ptr() for p in planes], *[p.data_ptr() for p in rec], out.data_ptr()), name)
         n_rows = self.lib.fcu_wpp_rows(self.h)
         for r in range(n_rows):
             self._keep[first_chain + r] = (planes, rec, out)
+            if p_slice:
+                self._bind_refs(first_chain + r, ref, refs, ref_pocs, poc, col_ref_pocs, col)
+        if p_slice and search_state is not None:
+            self.set_search_state(first_chain, search_state)
         return n_rows, rec, out
 
     def compress_wpp(self, first, n, stream=None):

@@ -10,9 +10,15 @@ reference's lowdelay configuration; one batched call for all clips) -> fcu_pad_r
 Across GPUs the reference picture is the only data a rank would need from another one (one copy per picture, SURVEY.md 8e);
 with whole clips per rank there is none.
 
+WaveFrontSynchro (wpp=True): every picture is one slice whose CTU rows are chains (fcu_wpp_begin for POC 0, fcu_wpp_begin_p
+for the P pictures), clip s, row k is chain s * n_rows + k, and the rows of all clips go in one fcu_compress_wpp launch; the
+loop filters and the reference padding are those of a one-slice picture.
+
 TZ search state: HM's encoder carries the integer vector of its last 2Nx2N search (TEncSearch::m_integerMv2Nx2N) across slices
-and pictures.  The slice chains of this driver run side by side and start it from zero; the difference shows only for a slice
-whose first CTU is too small for a 64x64 CU (fcu_chain_get / set_search_state for callers that need HM's value).
+and pictures.  Without WPP, the slice chains of this driver run side by side and start it from zero; the difference shows only
+for a slice whose first CTU is too small for a 64x64 CU (fcu_chain_get / set_search_state for callers that need
+HM's value).  With WPP the launch hands it from row to row exactly, and the driver carries it from picture to picture as HM
+does: the last row chain's state becomes the next picture's row-0 state.
 
 Context-table choice of a P picture (cabac_init_flag): HM initialises a P slice from the B-slice tables when
 TEncSbac::determineCabacInitIdx picked them after the previous slice (TEncSlice.cpp:1750-1753).  That choice is made on the
@@ -41,17 +47,23 @@ def ref_pocs(poc, n_refs, rps="hm"):
 
 class LowDelayPDecider:
     """`n_clips` clips of width x height decided picture by picture on one GPU.
-    slice_ctus: CTUs per slice (HM SliceMode 1); None = one slice per picture (the reference configuration)."""
+    slice_ctus: CTUs per slice (HM SliceMode 1); None = one slice per picture (the reference configuration).
+    wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm"):
+                 n_refs=1, rps="hm", wpp=False):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above)."""
+        if wpp and slice_ctus:
+            raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None)")
+        self.wpp = wpp
         self.width, self.height, self.base_qp, self.n_clips, self.search_range = width, height, base_qp, n_clips, search_range
         n_ctu = ((width + 63) // 64) * ((height + 63) // 64)
         self.slice_ctus = slice_ctus if slice_ctus else n_ctu
         self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
-        self.eng = _engine.CuEngine(width, height, max_chains=n_clips * self.n_slices, device=device)
+        self.n_chains = (height + 63) // 64 if wpp else self.n_slices          # chains per picture: rows (WPP) or slices
+        self.search_state = [None] * n_clips             # WPP: m_integerMv2Nx2N after each clip's last picture
+        self.eng = _engine.CuEngine(width, height, max_chains=n_clips * self.n_chains, device=device)
         self.do_deblock = deblock
         self.tmvp, self.fast_search = tmvp, fast_search    # TMVPMode / FastSearch of the reference cfg (TZ search by default)
         self.amp = amp                                   # AMP of the reference cfg (asymmetric motion partitions)
@@ -84,12 +96,17 @@ class LowDelayPDecider:
         res = []
         rl = ref_pocs(poc, self.n_refs, self.rps)
         for s, f in enumerate(frames):
-            first = s * self.n_slices
+            first = s * self.n_chains
             ref = self.ref[s] if fp.slice_type == _engine.SLICE_P else None
             col = self.col[s] if fp.tmvp else None
             kw = dict(ref=ref)
             if ref is not None and self.n_refs > 1:
                 kw = dict(refs=[self.dpb[s][q][0] for q in rl], ref_pocs=rl, poc=poc, col_ref_pocs=self.dpb[s][rl[0]][1])
+            if self.wpp:
+                state = self.search_state[s] if fp.slice_type == _engine.SLICE_P else None
+                _, rec, out = eng.init_wpp_picture(first, f, fp.qp, params=fp, col=col, search_state=state, **kw)
+                res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
+                continue
             rec, out = eng.init_chain(first, f, fp.qp, slice_ctus=self.slice_ctus if self.n_slices > 1 else 0, params=fp, col=col, **kw)
             planes = eng._keep[first][0]
             for k in range(self.n_slices):
@@ -99,7 +116,12 @@ class LowDelayPDecider:
                     a = k * self.slice_ctus
                     eng.set_range(first + k, a, min(self.slice_ctus, eng.n_ctu - a))
             res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
-        eng.compress_chains(0, self.n_clips * self.n_slices, self.slice_ctus)
+        if self.wpp:
+            eng.compress_wpp(0, self.n_clips * self.n_chains)
+            for s, r in enumerate(res):                      # HM's state after the picture: the last row's (fcu_wpp_begin_p)
+                r["search_state"] = self.search_state[s] = eng.search_state(r["first"] + self.n_chains - 1)
+        else:
+            eng.compress_chains(0, self.n_clips * self.n_slices, self.slice_ctus)
         for s, r in enumerate(res):
             r["rec_unfiltered"] = [p.clone() for p in r["rec"]]
             if self.do_deblock:

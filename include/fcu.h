@@ -27,9 +27,11 @@
  *   TEncSampleAdaptiveOffset::SAOProcess           fcu_sao (statistics, per-CTU parameter decision, offset pass) +
  *     (TEncSampleAdaptiveOffset.cpp:257,              fcu_sao_enabled / fcu_sao_update_rate (decidePicParams and the
  *      TEncGOP.cpp:1427-1441)                         m_saoDisabledRate bookkeeping across pictures, :363-395,895-917)
- *   WaveFrontSynchro=1 row loop of                 fcu_wpp_begin (one chain per CTU row of a one-slice I picture),
- *     TEncSlice::compressSlice                       fcu_compress_wpp (every row of whole pictures in one launch,
- *     (TEncSlice.cpp:1386-1411,1514-1517)            a row waiting for the row above), fcu_wpp_rows
+ *   WaveFrontSynchro=1 row loop of                 fcu_wpp_begin / fcu_wpp_begin_p (one chain per CTU row of a
+ *     TEncSlice::compressSlice                       one-slice I / P picture), fcu_compress_wpp (every row of whole
+ *     (TEncSlice.cpp:1386-1411,1514-1517)            pictures in one launch, a row waiting for the row above), fcu_wpp_rows
+ *     + m_integerMv2Nx2N across rows              (P: the row above's TZ start vectors, taken in the launch)
+ *     (TEncSearch.cpp:3833-3842)
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -174,11 +176,19 @@ int  fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_strea
  * slice, so every earlier CTU stays available as a neighbour, and each CTU row restarts its contexts (resetEntropy) from the
  * state saved after the second CTU of the row above (contexts only; a one-CTU-wide picture keeps the plain reset).  Row r may
  * decide CTU x once row r-1 has finished CTU x+1: a picture of W x H CTUs is H chains with a critical path of W + 2(H-1) CTUs.
- * fcu_wpp_begin binds chains [first_chain, first_chain + fcu_wpp_rows(c)) to the CTU rows of ONE picture, top to bottom (the
- * arguments of fcu_chain_begin; the rows share the planes and dev_out).  Built for I slices with one slice per picture:
- * fp->slice_type must be FCU_SLICE_I and fp->slice_ctus 0, else FCU_ERR_ARG -- P slices (HM carries m_integerMv2Nx2N from the
- * LAST CTU of the row above into a row, TEncSearch.cpp:3833-3842, a state a wavefront does not have yet) and WPP with SliceMode 1
- * are not supported; neither is writing substreams / entry points.  Too few chains: FCU_ERR_ARG.
+ * fcu_wpp_begin binds chains [first_chain, first_chain + fcu_wpp_rows(c)) to the CTU rows of ONE I picture, top to bottom (the
+ * arguments of fcu_chain_begin; the rows share the planes and dev_out); fp->slice_type must be FCU_SLICE_I.  fcu_wpp_begin_p
+ * takes the same arguments for ONE P picture; fp->slice_type must be FCU_SLICE_P.  Both need fp->slice_ctus 0 (WPP with
+ * SliceMode 1 is not supported; neither is writing substreams / entry points); otherwise, or with too few chains, FCU_ERR_ARG.
+ * P pictures: after fcu_wpp_begin_p, set the reference pictures (fcu_chain_set_reference or _set_references, and
+ * _set_collocated_pocs) and the collocated field (fcu_chain_set_collocated) on EVERY row chain, the same on each; set the search
+ * state (fcu_chain_set_search_state: what the previous picture left) on ROW 0 only.  Call order per row: fcu_chain_set_decision
+ * first (it rewrites the descriptor tail from the host copy, which resets the search state), the search state last.
+ * HM's m_integerMv2Nx2N crosses the rows of the picture (it walks them in raster order); the launch reproduces that exactly:
+ * a row whose first CTU is too small for a 64x64 CU waits for the whole row above and starts from its final search state, and
+ * every row ends with the slots it did not write taken from the row above, so fcu_chain_get_search_state on the LAST row chain
+ * returns HM's state after the picture (the next picture's row-0 state).  A row that begins on a full CTU writes every slot it
+ * reads first (its depth-0 2Nx2N searches), so only the partial bottom row, or a picture narrower than 64, waits longer.
  * fcu_chain_set_decision, fcu_chain_set_pu_trace, fcu_get_verify_counts (rows added up in chain order), fcu_chain_position and
  * fcu_get_ctx_state (the state after the chain's row) work on row chains as on slice chains; fcu_compress_chains /
  * fcu_compress_ctu / fcu_chain_set_range on a row chain return FCU_ERR_STATE. */
@@ -186,8 +196,12 @@ int  fcu_wpp_rows(const fcu_ctx *c);
 int  fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
                    const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
                    uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
+int  fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
+                     const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
+                     uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
 /* Decide every row chain in [first, first + n) to the end, in one launch on `hip_stream`.  The range must hold whole pictures
- * bound by fcu_wpp_begin and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin).  It may hold more
+ * bound by fcu_wpp_begin(_p) and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin; also for a P
+ * row without a reference picture, or whose references or collocated field differ from its row 0's).  It may hold more
  * chains than the GPU keeps resident.  Returns when the launch has finished; FCU_ERR_STATE if a row gave up waiting for the
  * row above (a bounded wait of 120 s; the pictures of the launch are then undefined). */
 int  fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream);
