@@ -158,6 +158,10 @@ template <class T> __device__ inline T fcu_uni(T v)
 #elif defined(FCU_PROFILE_RDOQ) || defined(FCU_PROFILE_DEPTH)   /* slots 11..15 belong to the sub-timers inside the serial RDOQ (FCU_PROFILE_DEPTH: 11..14 to the time spent at CU depth 0..3 without its sub-CUs) in these variants */
 #define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
+#elif defined(FCU_PROFILE_RMD)   /* RMD variant: slots 11..14 belong to the sub-timers of rmd() and to the reference build of the first pass (FCU_MTOC) */
+#define FCU_MTOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_COUNT(E_, idx, n) do { } while (0)
 #else
 #define FCU_TOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { (E_).C->prof[idx] += (unsigned long long)(n); } while (0)
@@ -173,6 +177,9 @@ template <class T> __device__ inline T fcu_uni(T v)
 #endif
 #ifndef FCU_ITOC
 #define FCU_ITOC(E_, v, idx) do { } while (0)
+#endif
+#ifndef FCU_MTOC
+#define FCU_MTOC(E_, v, idx) do { } while (0)
 #endif
 
 #include "fcu_tables.h"
@@ -369,6 +376,10 @@ struct Shared {
     uint32_t sad[36];                               /* RMD SATD per mode; [35] SSE accumulator of a TU trial */
   };
   int dc;
+  /* hand-over of ref / reff / dc from rmd() to the first pass of the same PU: ref_key(x, y, log2) of the luma block whose
+   * samples they hold, or -1.  Set by rmd() only; build_ref and chroma_leaf_refs5 (which overwrite the arrays) clear it, the
+   * first pass consumes it.  Anyone who finds -1, or another block's key, builds the samples himself. */
+  int ref_tag;
   int best_idx[4], reco_best_idx[4];               /* which of cu[d][0/1] / reco[d][0/1] is "best" */
   /* PU / TU mailbox written by serial blocks */
   union {
@@ -418,6 +429,14 @@ enum { CAB_GOON = 0, CAB_CUR0 = 1, CAB_LANE0 = 1 + (MAXDEPTH + 1) };
 enum { EST_CODERS = 7 };
 static_assert(EST_CODERS * sizeof(Cabac) >= NCTX_INTRA * 2 * sizeof(uint32_t) && EST_CODERS <= MAXLC, "est table does not fit its lane coders");
 #define FCU_EST ((uint32_t *)&g_S.cab[CAB_LANE0 + MAXLC - EST_CODERS])
+/* The RMD borrows the lane coders too (none is live between the PUs of a CU: a PU's winner is re-coded before the next PU's
+ * RMD starts): the row-transformed lines of the (mode, line) items of one wave iteration, 64 x 8 int16, and the 35 mode costs
+ * the candidate ranking reads. */
+enum { RMD_STAGE_BYTES = 64 * 8 * 2, RMD_COST_BYTES = 35 * 8 };
+static_assert(RMD_STAGE_BYTES + RMD_COST_BYTES <= MAXLC * sizeof(Cabac) && (CAB_LANE0 * sizeof(Cabac)) % 8 == 0, "RMD staging does not fit the lane coders");
+#define FCU_RMD_STAGE ((int16_t *)&g_S.cab[CAB_LANE0])
+#define FCU_RMD_COST ((double *)((char *)&g_S.cab[CAB_LANE0] + RMD_STAGE_BYTES))
+FCU_DEV int ref_key(int px, int py, int log2) { return px | (py << 13) | (log2 << 26); }
 #ifdef FCU_EMU
 static Shared g_S;
 #else
@@ -1538,6 +1557,7 @@ FCU_DEV FCU_NOINLINE void build_ref(int comp, int px, int py, int log2, int want
   const uint8_t *rec = E.C->rec[comp]; const int stride = E.C->stride[comp];
   uint8_t *ref = g_S.ref, *avail = (uint8_t *)g_S.colsum;    /* availability flags staged in colsum (>= 257 bytes) */
   FCU_FOR_LANES {
+    if (lane == 0) g_S.ref_tag = -1;
     for (int i = lane; i < total; i += 64) {
       int a, v = 0;
       if (i < 2 * N) { const int y = 2 * N - 1 - i; a = unit_available(E, lx0 - 4, ((py + y) / unit * unit) << sh, lx0, ly0); if (a) v = rec[(py + y) * stride + px - 1]; }
@@ -2341,54 +2361,173 @@ FCU_DEV uint32_t satd_unit(const uint8_t *org, int log2, int mode, int dc, int b
   return (uint32_t)(USZ == 8 ? ((s + 2) >> 2) : ((s + 1) >> 1));
 }
 
+/* Order in which the RMD deals the modes to the lanes: planar, DC and the two pure directions first, so that the wave
+ * iterations after the first hold general angular modes only and pred_pixel's other branches are skipped by the whole wave. */
+FCU_DEV int rmd_mode_of(int j) { return j < 2 ? j : j == 2 ? HOR : j == 3 ? VER : j < 12 ? j - 2 : j < 27 ? j - 1 : j; }
+
+/* One line of the prediction of an N x N luma block, N <= 8: out[k] = pred_pixel(ref, LOG2, mode, 1, dc, X, Y) with
+ * (X, Y) = (k, line) for planar, DC and the vertical modes 18..34 (a row), (line, k) for the horizontal modes 2..17 (a column).
+ * Along such a line deltaPos, and with it the sample offset and the interpolation weight, are constants, and neighbouring
+ * samples share a reference sample.  Same arithmetic as pred_pixel, which stays the definition (checked in the emulator). */
+template <int LOG2>
+FCU_DEV void pred_line(const uint8_t *ref, int mode, int dc, int line, int *out)
+{
+  constexpr int N = 1 << LOG2;
+  static_assert(N <= 8, "edge filters of DC / pure directions assumed on (N <= 16)");
+  const uint8_t *corner = ref + 2 * N;
+  if (mode < 2) {
+#pragma unroll
+    for (int k = 0; k < N; k++) out[k] = pred_pixel(ref, LOG2, mode, 1, dc, k, line);
+    return;
+  }
+  const int isVer = mode >= 18, ms = isVer ? 1 : -1;
+  const int angMode = isVer ? mode - VER : -(mode - HOR), absAng = iabs(angMode);
+  if (absAng == 0) {
+#pragma unroll
+    for (int k = 0; k < N; k++) out[k] = corner[ms * (k + 1)];
+    out[0] = clip8(out[0] + ((corner[-ms * (line + 1)] - corner[0]) >> 1));
+  } else {
+    const int angAbs = (int)((0x2069544d245080ull >> (6 * absAng)) & 63);
+    const int invAngle = (int)(((absAng <= 4 ? 0x13b0e38ccd000ull : 0x8004ec30c1e2ull) >> (13 * ((absAng - 1) & 3))) & 8191);
+    const int angle = angMode < 0 ? -angAbs : angAbs;
+    const int deltaPos = (line + 1) * angle, di = deltaPos >> 5, df = deltaPos & 31;
+    int r[N + 1];
+#pragma unroll
+    for (int k = 0; k <= N; k++) {
+      const int i = k + di + 1;
+      r[k] = (k == N && !df) ? 0 : (i >= 0) ? corner[ms * i] : corner[-ms * ((128 + (-i) * invAngle) >> 8)];
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) out[k] = df ? (((32 - df) * r[k] + df * r[k + 1] + 16) >> 5) : r[k];
+  }
+#ifdef FCU_EMU
+  for (int k = 0; k < N; k++) FCU_CHECK(out[k] == pred_pixel(ref, LOG2, mode, 1, dc, isVer ? k : line, isVer ? line : k));
+#endif
+}
+
+template <int N> FCU_DEV void hadamard_line(int *v)
+{
+#pragma unroll
+  for (int len = 1; len < N; len <<= 1)
+#pragma unroll
+    for (int i = 0; i < N; i += 2 * len)
+#pragma unroll
+      for (int j = i; j < i + len; j++) { const int a = v[j], b = v[j + len]; v[j] = a + b; v[j + len] = a - b; }
+}
+
+/* RMD of an 8x8 or 4x4 PU (one Hadamard block per mode): the work item is (mode, line), 35 * N of them, 64 per wave iteration
+ * (280 of 320 lane slots for 8x8, 140 of 192 for 4x4, against 35 of 64 with a whole block per lane).  A lane predicts its line
+ * (pred_line), subtracts it from the source and transforms it; the lines of a block meet in the staging area, where lane
+ * (block, k) transforms sample k of its N lines and adds the magnitudes into g_S.sad[mode] (the raw sum: the caller rounds).
+ * Horizontal modes are dealt by columns: the transform is separable, so which direction runs first does not matter. */
+template <int LOG2>
+FCU_DEV void rmd_satd_small(const uint8_t *org)
+{
+  constexpr int N = 1 << LOG2, ITEMS = 35 * N;
+  int16_t *stage = FCU_RMD_STAGE;
+  for (int base = 0; base < ITEMS; base += 64) {
+    FCU_FOR_LANES {
+      const int it = base + lane;
+      if (it < ITEMS) {
+        const int mode = rmd_mode_of(it >> LOG2), line = it & (N - 1);
+        int v[N];
+        pred_line<LOG2>(use_filtered_ref(mode, LOG2, 1) ? g_S.reff : g_S.ref, mode, g_S.dc, line, v);
+        if (mode >= 2 && mode < 18) {
+#pragma unroll
+          for (int k = 0; k < N; k++) v[k] = (int)org[k * 64 + line] - v[k];
+        } else {
+          uint8_t o[N];
+          __builtin_memcpy(o, org + line * 64, N);
+#pragma unroll
+          for (int k = 0; k < N; k++) v[k] = (int)o[k] - v[k];
+        }
+        hadamard_line<N>(v);
+#pragma unroll
+        for (int k = 0; k < N; k++) stage[lane * N + k] = (int16_t)v[k];     /* |v| <= 8 * 255 */
+      }
+    }
+    FCU_FOR_LANES {
+      const int blk = lane >> LOG2, k = lane & (N - 1), it = base + blk * N;
+      if (it < ITEMS) {
+        int v[N];
+#pragma unroll
+        for (int l = 0; l < N; l++) v[l] = stage[(blk * N + l) * N + k];
+        hadamard_line<N>(v);
+        int sum = 0;
+#pragma unroll
+        for (int l = 0; l < N; l++) sum += iabs(v[l]);
+        FCU_ATOMIC_ADD(&g_S.sad[rmd_mode_of(it >> LOG2)], (uint32_t)sum);
+      }
+    }
+  }
+}
+
 FCU_DEV FCU_NOINLINE void rmd(CuObj *cu, uint32_t tu_k)
 {
   const Env E = env_get(); cu = FCU_UNI(cu); const TU tu = tu_of_key(FCU_UNI(tu_k));
   Scratch *G = E.G; const Params &P = E.C->p;
   const int d = cu->depth_cu, N = 1 << tu.log2, log2 = tu.log2;
-  build_ref(0, cu->x + tu.x, cu->y + tu.y, log2, 1);
+  { FCU_TIC(tm_); build_ref(0, cu->x + tu.x, cu->y + tu.y, log2, 1); FCU_MTOC(E, tm_, 11); }
   const uint8_t *org = G->org[d].y + tu.y * 64 + tu.x;
-  /* one (mode, Hadamard block) unit per lane, entirely in registers: no staging, no barrier between the stages */
-  FCU_FOR_LANES { if (lane < 36) g_S.sad[lane] = 0; }
+  FCU_TIC(tm1_);
   FCU_FOR_LANES {
-    const int dc = g_S.dc;
-    if (N >= 8) {
-      const int bpr = N >> 3, nblk = bpr * bpr;
-      for (int u = lane; u < 35 * nblk; u += 64) { const int mode = u / nblk, blk = u - mode * nblk; FCU_ATOMIC_ADD(&g_S.sad[mode], satd_unit<8>(org, log2, mode, dc, (blk % bpr) * 8, (blk / bpr) * 8)); }
-    } else {
-      for (int u = lane; u < 35; u += 64) FCU_ATOMIC_ADD(&g_S.sad[u], satd_unit<4>(org, log2, u, dc, 0, 0));
+    if (lane < 36) g_S.sad[lane] = 0;
+    if (lane == 0) {                                       /* the most probable modes: neighbour CU data only */
+      int preds[3];
+      g_S.n_mpm = intra_dir_predictor(E, cu, tu.part, preds);
+      g_S.preds[0] = preds[0]; g_S.preds[1] = preds[1]; g_S.preds[2] = preds[2];
+      g_S.ref_tag = ref_key(cu->x + tu.x, cu->y + tu.y, log2);   /* the first pass of this PU takes the samples over */
     }
   }
-  /* mode bits + sorted insert (serial) */
-  FCU_SERIAL {
-    int preds[3];
-    const int nm = intra_dir_predictor(E, cu, tu.part, preds);
-    g_S.preds[0] = preds[0]; g_S.preds[1] = preds[1]; g_S.preds[2] = preds[2]; g_S.n_mpm = nm;
-    const Cabac *cb = slot_ptr(E, d, CI_CURR_BEST);
-    const uint64_t carry = cb->frac & 32767;               /* loadIntraDirMode + resetBits, TEncSearch.cpp:5313-5340 */
-    int numFull = k_rd_mode_num[log2 - 2];
-    double *candCost = g_S.cand_cost;                    /* in LDS: the sorted insert indexes it with run-time subscripts */
-    for (int i = 0; i < numFull; i++) candCost[i] = FCU_MAX_DOUBLE;
-    for (int mode = 0; mode < 35; mode++) {
+  if (N >= 16) {
+    /* one (mode, Hadamard block) unit per lane, entirely in registers; block index fastest, so that the lanes of an iteration
+     * share the mode (64x64) or hold 4 / 16 modes of one class */
+    FCU_FOR_LANES {
+      const int dc = g_S.dc;
+      const int bpr = N >> 3, nblk = bpr * bpr;
+      for (int u = lane; u < 35 * nblk; u += 64) { const int j = u / nblk, blk = u - j * nblk, mode = rmd_mode_of(j); FCU_ATOMIC_ADD(&g_S.sad[mode], satd_unit<8>(org, log2, mode, dc, (blk % bpr) * 8, (blk / bpr) * 8)); }
+    }
+  } else if (N == 8) rmd_satd_small<3>(org);
+  else rmd_satd_small<2>(org);
+  FCU_MTOC(E, tm1_, 12);
+  FCU_TIC(tm2_);
+  /* Candidate list (xUpdateCandList): the insertion with a strict '<' is a stable sort by cost, so mode m ends up at position
+   * #{m' : cost[m'] < cost[m]} + #{m' < m : cost[m'] == cost[m]}.  One lane per mode prices its mode, then ranks it against the
+   * 35 costs; the first numRmd positions are the list. */
+  const int numRmd = k_rd_mode_num[log2 - 2];
+  double *cost35 = FCU_RMD_COST;
+  FCU_FOR_LANES {
+    if (lane < 35) {
+      const int mode = lane;
       int predIdx = -1;
-      for (int i = 0; i < 3; i++) if (mode == preds[i]) predIdx = i;
+      for (int i = 0; i < 3; i++) if (mode == g_S.preds[i]) predIdx = i;
+      const uint64_t carry = slot_ptr(E, d, CI_CURR_BEST)->frac & 32767;   /* loadIntraDirMode + resetBits, TEncSearch.cpp:5313-5340 */
       const uint64_t fr = carry + (uint64_t)ctx_bits(CAB_CUR0 + d, CTX_INTRA_LUMA, predIdx != -1) + (uint64_t)32768 * (uint64_t)(predIdx != -1 ? (predIdx ? 2 : 1) : 5);
       const uint32_t modeBits = (uint32_t)(fr >> 15);
-      const double cost = (double)g_S.sad[mode] + (double)modeBits * P.sqrt_lambda;
-      int shift = 0;
-      while (shift < numFull && cost < candCost[numFull - 1 - shift]) shift++;
-      if (shift != 0) {
-        for (int i = 1; i < shift; i++) { g_S.rd_mode[numFull - i] = g_S.rd_mode[numFull - 1 - i]; candCost[numFull - i] = candCost[numFull - 1 - i]; }
-        g_S.rd_mode[numFull - shift] = mode; candCost[numFull - shift] = cost;
-      }
+      uint32_t sad = g_S.sad[mode];
+      if (N == 8) sad = (sad + 2) >> 2; else if (N == 4) sad = (sad + 1) >> 1;   /* xCalcHADs8x8 / xCalcHADs4x4 round the block's sum */
+      cost35[mode] = (double)sad + (double)modeBits * P.sqrt_lambda;
     }
+  }
+  FCU_FOR_LANES {
+    if (lane < 35) {
+      const double c = cost35[lane];
+      int rank = 0;
+      for (int m = 0; m < 35; m++) { const double o = cost35[m]; rank += (o < c || (o == c && m < lane)) ? 1 : 0; }
+      if (rank < numRmd) { g_S.rd_mode[rank] = lane; g_S.cand_cost[rank] = c; }
+    }
+  }
+  FCU_SERIAL {
+    int numFull = numRmd;
+    const int nm = g_S.n_mpm;
     for (int j = 0; j < nm; j++) {
       int inc = 0;
-      for (int i = 0; i < numFull; i++) inc |= (preds[j] == g_S.rd_mode[i]);
-      if (!inc) g_S.rd_mode[numFull++] = preds[j];
+      for (int i = 0; i < numFull; i++) inc |= (g_S.preds[j] == g_S.rd_mode[i]);
+      if (!inc) g_S.rd_mode[numFull++] = g_S.preds[j];
     }
     g_S.n_rd = numFull;
   }
+  FCU_MTOC(E, tm2_, 13);
 }
 
 /* ======================================================================================== */
@@ -2410,8 +2549,11 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
   const int useDst = log2 == 2;
   const uint8_t *org = G->org[d].y + tu.y * 64 + tu.x;
   /* reference samples are shared by all candidates: the TU is the whole PU */
-  build_ref(0, cu->x + tu.x, cu->y + tu.y, log2, 1);
+  /* ... and rmd() has just built them for this very block, unless the caller came another way (the tag says) */
+  const int haveRefs = FCU_UNI(g_S.ref_tag) == ref_key(cu->x + tu.x, cu->y + tu.y, log2);
+  if (!haveRefs) { FCU_TIC(tm_); build_ref(0, cu->x + tu.x, cu->y + tu.y, log2, 1); FCU_MTOC(E, tm_, 14); }
   FCU_FOR_LANES {                                            /* prediction + residual per candidate */
+    if (lane == 0) g_S.ref_tag = -1;                         /* consumed: the quantisation below reuses the arrays */
     const int dc = g_S.dc;
     for (int i = lane; i < nc * n2; i += 64) {
       const int cnd = i / n2, p = i - cnd * n2, y = p >> log2, x = p & (N - 1), mode = g_S.rd_mode[cnd];
@@ -2760,6 +2902,7 @@ FCU_DEV void chroma_leaf_refs5(const Env E, const CuObj *cu, int comp, int px, i
   const int cx0 = cu->x >> 1, cy0 = cu->y >> 1, cs = (CTU >> cu->depth_cu) >> 1;
   uint8_t *avail = (uint8_t *)g_S.colsum;
   FCU_FOR_LANES {
+    if (lane == 0) g_S.ref_tag = -1;                         /* ref5b overlays ref / reff */
     for (int i = lane; i < total; i += 64) {
       int a, x, y;
       if (i < 2 * N) { y = py + 2 * N - 1 - i; x = px - 1; a = unit_available(E, lx0 - 4, (y / 2 * 2) << 1, lx0, ly0); }
@@ -3367,7 +3510,7 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
   const int x = (ctuRsAddr % C->w_ctu) * CTU, y = (ctuRsAddr / C->w_ctu) * CTU;
   const int col = ctuRsAddr % C->w_ctu;
   const bool row_start = WPP && col == 0 && ctuRsAddr != sliceStart;
-  FCU_SERIAL { g_S.env = E; if (ctuRsAddr == sliceStart || row_start) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
+  FCU_SERIAL { g_S.env = E; g_S.ref_tag = -1; if (ctuRsAddr == sliceStart || row_start) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
   if (row_start && C->w_ctu >= 2) {
     const uint8_t *src = C->wpp_sync_in;
     FCU_FOR_LANES { Cabac *d = slot_ptr(E, 0, CI_CURR_BEST); for (int i = lane; i < NCTX; i += 64) d->ctx[i] = src[i]; }   /* lane-indexed: vector loads */
