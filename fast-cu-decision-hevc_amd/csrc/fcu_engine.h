@@ -74,6 +74,9 @@ template <class T> static inline T fcu_emu_uni(T v, int site, int line)
 #define FCU_HBM
 #define FCU_FLOOR(x) floor(x)
 #define FCU_CHECK(c) do { if (!(c)) { fprintf(stderr, "FCU_CHECK failed: %s (line %d)\n", #c, __LINE__); abort(); } } while (0)
+/* intra candidate CUs by the way their bits were found (check_rd_cost_intra): merged from the search's coders with the chroma
+ * search's own coder, merged with a chroma-only walk, walked in full */
+static unsigned long long g_emu_cu_paths[3] = { 0, 0, 0 };
 #else
 #define FCU_DEV __device__ static
 #define FCU_MEMBER __device__ inline
@@ -162,6 +165,12 @@ template <class T> __device__ inline T fcu_uni(T v)
 #define FCU_MTOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
+#elif defined(FCU_PROFILE_CUSYN)   /* CU-syntax variant: slots 11..14 split section 7 (FCU_STOC: 11 / 12 = its 2Nx2N / NxN calls, 13 / 14 = code_coeff_nxn of luma / chroma levels inside the 2Nx2N calls); 15 counts the CUs per path, 21 bits each (FCU_SPATH) */
+#define FCU_STOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_SPATH(E_, path) do { if (threadIdx.x == 0) (E_).C->prof[15] += 1ull << (21 * (path)); } while (0)
+#define FCU_S7_COEFF(E_, v, comp) do { if (g_S.prof_s7 == 1) FCU_STOC(E_, v, (comp) ? 14 : 13); } while (0)   /* inside a 2Nx2N call of section 7 only */
+#define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_COUNT(E_, idx, n) do { } while (0)
 #else
 #define FCU_TOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { (E_).C->prof[idx] += (unsigned long long)(n); } while (0)
@@ -180,6 +189,11 @@ template <class T> __device__ inline T fcu_uni(T v)
 #endif
 #ifndef FCU_MTOC
 #define FCU_MTOC(E_, v, idx) do { } while (0)
+#endif
+#ifndef FCU_STOC
+#define FCU_STOC(E_, v, idx) do { } while (0)
+#define FCU_SPATH(E_, path) do { } while (0)
+#define FCU_S7_COEFF(E_, v, comp) do { } while (0)
 #endif
 
 #include "fcu_tables.h"
@@ -352,8 +366,9 @@ struct TU { int log2, tr_depth, part, nparts, x, y, off_y, cw, cwo, cx, cy, c_tr
 /* per-chain LDS */
 struct Shared {
   /* hot coders, one LDS array so that coder ids index it directly:
-   * [CAB_GOON] go-on coder, [CAB_CUR0+d] = [depth][CI_CURR_BEST], [CAB_LANE0+k] lane-private trial coders */
-  Cabac cab[1 + (MAXDEPTH + 1) + MAXLC];
+   * [CAB_GOON] go-on coder, [CAB_CUR0+d] = [depth][CI_CURR_BEST], [CAB_LANE0+k] lane-private trial coders,
+   * [CAB_LUMA] the coder after the walk of the luma encoding est_intra_pred_luma chose for a 2Nx2N CU */
+  Cabac cab[1 + (MAXDEPTH + 1) + MAXLC + 1];
   uint8_t ref5[5][68]; int dc5[5]; uint32_t cm_dist[5];     /* chroma: per-mode reference samples (N <= 16) */
   /* Three tenants that are never live together (8 KB of LDS per chain = 20 chains per CU, five waves per SIMD):
    *  - reference samples of the block being predicted (+ the availability flags that build them): dead once the
@@ -420,10 +435,17 @@ struct Shared {
   double cand_cost[12];                             /* RMD candidate costs (CandCostList, TEncSearch.cpp:2289) */
   uint32_t c64_dist[5]; uint8_t c64_cbf[5][4]; int c64_valid;      /* 64x64 first pass: per-candidate distortion / cbf of its four TUs */
   uint64_t q_frac[5], t_frac;                       /* exact (Q15) bit counts of the chosen RQT subtrees per recursion level / of the last walk */
+  uint32_t q_bins[5], t_bins;                       /* ... and their bin counts */
+  /* luma-final state of a 2Nx2N intra CU, from est_intra_pred_luma to check_rd_cost_intra: cab[CAB_LUMA] holds the contexts,
+   * lf_frac the Q15 count (with the remainder the search started from), lf_bins the bins; lf_valid = 0: none, walk the CU */
+  uint64_t lf_frac; uint32_t lf_bins; int lf_valid;
   double dec_j0, dec_j1; int dec_cnt, dec_flip;     /* fork hooks: J0 / J1 / Num_OBF / bPartition_True of the CU being closed */
+#ifdef FCU_PROFILE_CUSYN
+  int prof_s7;                                      /* section 7 in flight: 1 = of a 2Nx2N CU, 2 = of an NxN CU, 0 = none (the CTU replay walks the same code) */
+#endif
 };
 
-enum { CAB_GOON = 0, CAB_CUR0 = 1, CAB_LANE0 = 1 + (MAXDEPTH + 1) };
+enum { CAB_GOON = 0, CAB_CUR0 = 1, CAB_LANE0 = 1 + (MAXDEPTH + 1), CAB_LUMA = CAB_LANE0 + MAXLC };
 /* RDOQ's rate table (NCTX_INTRA x 2 words) borrows lane coders [MAXLC-7, MAXLC): est_build() fills it before the RDOQ of a
  * batch, the bit count that follows is the first to load those coders, and nothing reads the table afterwards. */
 enum { EST_CODERS = 7 };
@@ -1866,10 +1888,12 @@ FCU_DEV FCU_NOINLINE uint32_t leaf_luma_bits(int c, const CuObj *cu, uint32_t tu
   return cab_bits(c);
 }
 
-/* final-order CU syntax: encodeCoeff / xEncodeTransform, TEncEntropy.cpp:201-400 */
-FCU_DEV FCU_NOINLINE void encode_transform(int c, const CuObj *cu, int cuPart, uint32_t root_k)
+/* final-order CU syntax: encodeCoeff / xEncodeTransform, TEncEntropy.cpp:201-400.  withLuma = 0 leaves out everything the
+ * luma search's walk has coded (subdivision flags, luma cbf, luma levels): the chroma cbf bins and the Cb / Cr levels
+ * leaf by leaf, in the order of the full walk (check_rd_cost_intra merges the two) */
+FCU_DEV FCU_NOINLINE void encode_transform(int c, const CuObj *cu, int cuPart, uint32_t root_k, int withLuma)
 {
-  const Env E = env_get(); c = FCU_UNI(c); cu = FCU_UNI(cu); cuPart = FCU_UNI(cuPart); const TU root = tu_of_key(FCU_UNI(root_k));
+  const Env E = env_get(); c = FCU_UNI(c); cu = FCU_UNI(cu); cuPart = FCU_UNI(cuPart); const TU root = tu_of_key(FCU_UNI(root_k)); withLuma = FCU_UNI(withLuma);
   TU *st = g_S.wk_st; int *ci = g_S.wk_ci; int sp = 0;
   st[0] = root; ci[0] = -1;
   while (sp >= 0) {
@@ -1880,7 +1904,7 @@ FCU_DEV FCU_NOINLINE void encode_transform(int c, const CuObj *cu, int cuPart, u
       else if (tu.log2 > LOG2_MAXTU) { }
       else if (tu.log2 == LOG2_MINTU) { }
       else if (tu.log2 == min_tu_log2_in_cu(cu->depth[part], cu->part_size[part])) { }
-      else cab_bin(c, subdiv, CTX_SUBDIV + 5 - tu.log2);
+      else if (withLuma) cab_bin(c, subdiv, CTX_SUBDIV + 5 - tu.log2);
       const int first = trIdx == 0;
       for (int comp = 1; comp < 3; comp++)
         if (first || tu.c_code_all)
@@ -1889,14 +1913,14 @@ FCU_DEV FCU_NOINLINE void encode_transform(int c, const CuObj *cu, int cuPart, u
             cab_bin(c, (cu->cbf[comp][cuPart + tu_part_c(tu)] >> lowest) & 1, CTX_CBF_CHROMA + trIdx);
           }
       if (!subdiv) {
-        cab_bin(c, (cu->cbf[0][part] >> trIdx) & 1, CTX_CBF_LUMA + (trIdx == 0 ? 1 : 0));
-        for (int comp = 0; comp < 3; comp++) {
+        if (withLuma) cab_bin(c, (cu->cbf[0][part] >> trIdx) & 1, CTX_CBF_LUMA + (trIdx == 0 ? 1 : 0));
+        for (int comp = withLuma ? 0 : 1; comp < 3; comp++) {
           if (comp && tu.cw == 0) continue;
           if (!((cu->cbf[comp][part] >> trIdx) & 1)) continue;
           const int log2 = comp ? ilog2(tu.cw) : tu.log2, pc = cuPart + (comp ? tu_part_c(tu) : tu.part);
           const int dir = comp ? chroma_final_mode(cu, pc) : cu->intra_dir[0][pc];
           const int16_t *coef = cu->coef[comp] + (comp ? (cuPart * 4 + tu.off_c) : (cuPart * 16 + tu.off_y));
-          code_coeff_nxn<1>(c, coef, 1, -1, log2, comp, coef_scan_idx(dir, log2, comp), cu->tskip[comp][pc], E.C->p, g_S.lane_abs[0]);
+          { FCU_TIC(ts_); code_coeff_nxn<1>(c, coef, 1, -1, log2, comp, coef_scan_idx(dir, log2, comp), cu->tskip[comp][pc], E.C->p, g_S.lane_abs[0]); FCU_S7_COEFF(E, ts_, comp); }
         }
         sp--; continue;
       }
@@ -1916,7 +1940,7 @@ FCU_DEV void encode_cu_syntax(const Env E, int c, const CuObj *cu, int cuPart, i
   code_intra_dir_luma(c, cu, cuPart, 1);
   code_intra_dir_chroma(c, cu->intra_dir[1][cuPart]);
   TU root; tu_root(root, depth);
-  encode_transform(c, cu, cuPart, tu_key(root));
+  encode_transform(c, cu, cuPart, tu_key(root), 1);
 }
 
 /* ======================================================================================== */
@@ -2162,7 +2186,7 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
   if (checkFirst && checkFull) checkSplit = 0;
   int checkTS = P.transform_skip && log2 == 2;
   if (P.ts_fast) checkTS = checkTS && (partSize == SIZE_NxN);
-  double singleCost = FCU_MAX_DOUBLE; uint32_t singleDist = 0, singleCbf = 0; int bestModeId = 0; uint64_t singleFrac = 0;
+  double singleCost = FCU_MAX_DOUBLE; uint32_t singleDist = 0, singleCbf = 0, singleBins = 0; int bestModeId = 0; uint64_t singleFrac = 0;
 
   if (checkFull) {
     if (checkTS) {
@@ -2174,11 +2198,11 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
         double tmpCost;
         if (modeId == 1 && tmpCbf == 0) tmpCost = FCU_MAX_DOUBLE;
         else {
-          { FCU_TIC(t12_); FCU_SERIAL { const uint64_t f0 = g_S.cab[CAB_GOON].frac & 32767; g_S.vc_bits[0] = leaf_luma_bits(CAB_GOON, cu, tu_key(tu)); g_S.t_frac = g_S.cab[CAB_GOON].frac - f0; } FCU_TOC(E, t12_, 12); }
+          { FCU_TIC(t12_); FCU_SERIAL { const uint64_t f0 = g_S.cab[CAB_GOON].frac & 32767; g_S.vc_bits[0] = leaf_luma_bits(CAB_GOON, cu, tu_key(tu)); g_S.t_frac = g_S.cab[CAB_GOON].frac - f0; g_S.t_bins = g_S.cab[CAB_GOON].bins; } FCU_TOC(E, t12_, 12); }
           tmpCost = FCU_UNI(rd_cost(P, g_S.vc_bits[0], tmpDist));
         }
         if (tmpCost < singleCost) {
-          singleCost = tmpCost; singleDist = tmpDist; singleCbf = tmpCbf; bestModeId = modeId; singleFrac = FCU_UNI(g_S.t_frac);
+          singleCost = tmpCost; singleDist = tmpDist; singleCbf = tmpCbf; bestModeId = modeId; singleFrac = FCU_UNI(g_S.t_frac); singleBins = FCU_UNI(g_S.t_bins);
           if (bestModeId == 0) { store_intra_result_qt(tu_key(tu), 0); FCU_FOR_LANES cab_copy(slot_ptr(E, fullDepth, CI_TEMP_BEST), &g_S.cab[CAB_GOON], lane); }
         }
         if (modeId == 0) FCU_FOR_LANES cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, fullDepth, CI_QT_TRAFO_ROOT), lane);
@@ -2196,8 +2220,8 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
          * from the same snapshot: take its levels, reconstruction, distortion, bits and coder state instead of
          * recomputing them (the candidate pools still hold them) */
         const int bv = reuseVc, N = 1 << log2, n2 = N * N, layer = LOG2_MAXTU - log2, cbf = FCU_UNI((int)(g_S.vc_abs[bv] > 0));
-        FCU_SERIAL { g_S.t_frac = g_S.cab[CAB_LANE0 + g_S.vc_slot[bv]].frac - (g_S.cab[CAB_GOON].frac & 32767); }   /* the lane coder started from this snapshot */
-        singleFrac = FCU_UNI(g_S.t_frac);
+        FCU_SERIAL { const Cabac *w = &g_S.cab[CAB_LANE0 + g_S.vc_slot[bv]]; g_S.t_frac = w->frac - (g_S.cab[CAB_GOON].frac & 32767); g_S.t_bins = w->bins; }   /* the lane coder started from this snapshot */
+        singleFrac = FCU_UNI(g_S.t_frac); singleBins = FCU_UNI(g_S.t_bins);
         FCU_FOR_LANES {
           for (int i = lane; i < n2; i += 64) {
             G->qt_coef[0][layer][tu.off_y + i] = (cbf && (i >> 4) <= (g_S.vc_last[bv] >> 4)) ? G->p_qscan[i * g_S.pu_nvc + bv] : (int16_t)0;
@@ -2215,10 +2239,11 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
         FCU_SERIAL {
           const uint64_t fprev = k ? G->c64_state[bv][k - 1].frac : (slot_ptr(E, d, CI_CURR_BEST)->frac & 32767);
           g_S.t_frac = G->c64_state[bv][k].frac - fprev;
+          g_S.t_bins = G->c64_state[bv][k].bins - (k ? G->c64_state[bv][k - 1].bins : 0u);
           g_S.vc_bits[0] = (uint32_t)(((fprev & 32767) + g_S.t_frac) >> 15);
           g_S.t_dist = G->c64_distk[bv][k];
         }
-        singleFrac = FCU_UNI(g_S.t_frac);
+        singleFrac = FCU_UNI(g_S.t_frac); singleBins = FCU_UNI(g_S.t_bins);
         FCU_FOR_LANES {
           for (int i = lane; i < n2; i += 64) {
             G->qt_coef[0][layer][tu.off_y + i] = G->c64_coef[bv][tu.off_y + i];
@@ -2235,8 +2260,8 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
         tu_trial(cu, tu_key(tu), 0, (CAB_GOON), 0);
         singleDist = FCU_UNI(g_S.t_dist);
         if (checkSplit) singleCbf = FCU_UNI((uint32_t)((cu->cbf[0][part] >> trDepth) & 1));
-        { FCU_TIC(t12_); FCU_SERIAL { const uint64_t f0 = g_S.cab[CAB_GOON].frac & 32767; g_S.vc_bits[0] = leaf_luma_bits(CAB_GOON, cu, tu_key(tu)); g_S.t_frac = g_S.cab[CAB_GOON].frac - f0; } FCU_TOC(E, t12_, 12); }
-        singleFrac = FCU_UNI(g_S.t_frac);
+        { FCU_TIC(t12_); FCU_SERIAL { const uint64_t f0 = g_S.cab[CAB_GOON].frac & 32767; g_S.vc_bits[0] = leaf_luma_bits(CAB_GOON, cu, tu_key(tu)); g_S.t_frac = g_S.cab[CAB_GOON].frac - f0; g_S.t_bins = g_S.cab[CAB_GOON].bins; } FCU_TOC(E, t12_, 12); }
+        singleFrac = FCU_UNI(g_S.t_frac); singleBins = FCU_UNI(g_S.t_bins);
         singleCost = FCU_UNI(rd_cost(P, g_S.vc_bits[0], singleDist));
       }
     }
@@ -2245,7 +2270,7 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
     if constexpr (LEVEL < 3) {
       if (checkFull) { FCU_FOR_LANES { cab_copy(slot_ptr(E, fullDepth, CI_QT_TRAFO_TEST), &g_S.cab[CAB_GOON], lane); } FCU_FOR_LANES { cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, fullDepth, CI_QT_TRAFO_ROOT), lane); } }
       else FCU_FOR_LANES cab_copy(slot_ptr(E, fullDepth, CI_QT_TRAFO_ROOT), &g_S.cab[CAB_GOON], lane);
-      FCU_SERIAL { g_S.q_dist[LEVEL + 1] = 0; g_S.q_cost[LEVEL + 1] = 0; g_S.q_frac[LEVEL + 1] = 0; }
+      FCU_SERIAL { g_S.q_dist[LEVEL + 1] = 0; g_S.q_cost[LEVEL + 1] = 0; g_S.q_frac[LEVEL + 1] = 0; g_S.q_bins[LEVEL + 1] = 0; }
       uint32_t splitCbf = 0;
       int chainOk = LEVEL == 0 && log2 == 6 && !checkFirst && FCU_UNI(g_S.c64_valid);   /* see the reuse branch above */
       for (int i = 0; i < 4; i++) {
@@ -2260,7 +2285,8 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
        * encodings (child 0 starts from this node's root state and, when this node begins the CU, also carries the
        * part-size / luma-mode bins; the subdivision and cbf contexts are indexed by TU size / depth), so the exact Q15
        * count is this node's own subdivision flag plus the children's counts, and the coder after the last child is
-       * the coder after the walk.  Not for the NxN root, whose walk leaves out the luma modes its children count. */
+       * the coder after the walk.  The bins add up the same way.  Not for the NxN root, whose walk leaves out the luma
+       * modes its children count. */
       const int sumBits = !(partSize == SIZE_NxN && trDepth == 0);
       FCU_FOR_LANES {
         if (splitCbf) for (int o = lane; o < tu.nparts; o += 64) cu->cbf[0][part + o] |= (uint8_t)(1 << trDepth);
@@ -2273,15 +2299,15 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
           if (sumBits) {
             g_S.cab[CAB_GOON].frac = f0; g_S.cab[CAB_GOON].bins = 0;
             if (log2 <= LOG2_MAXTU) cab_bin((CAB_GOON), 1, CTX_SUBDIV + 5 - log2);
-            g_S.cab[CAB_GOON].frac += g_S.q_frac[LEVEL + 1];
+            g_S.cab[CAB_GOON].frac += g_S.q_frac[LEVEL + 1]; g_S.cab[CAB_GOON].bins += g_S.q_bins[LEVEL + 1];
             g_S.vc_bits[0] = (uint32_t)(g_S.cab[CAB_GOON].frac >> 15);
           } else g_S.vc_bits[0] = intra_bits_qt((CAB_GOON), cu, tu_key(tu), 1, 0);
-          g_S.t_frac = g_S.cab[CAB_GOON].frac - f0;
+          g_S.t_frac = g_S.cab[CAB_GOON].frac - f0; g_S.t_bins = g_S.cab[CAB_GOON].bins;
         }
         FCU_TOC(E, t12_, 12);
       }
       const double splitCost = FCU_UNI(rd_cost(P, g_S.vc_bits[0], splitDist));
-      if (splitCost < singleCost) { FCU_SERIAL { g_S.q_dist[LEVEL] += splitDist; g_S.q_cost[LEVEL] += splitCost; g_S.q_frac[LEVEL] += g_S.t_frac; } return; }
+      if (splitCost < singleCost) { FCU_SERIAL { g_S.q_dist[LEVEL] += splitDist; g_S.q_cost[LEVEL] += splitCost; g_S.q_frac[LEVEL] += g_S.t_frac; g_S.q_bins[LEVEL] += g_S.t_bins; } return; }
       FCU_FOR_LANES {
         cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, fullDepth, CI_QT_TRAFO_TEST), lane);
         for (int i = lane; i < tu.nparts; i += 64) { cu->tr_idx[part + i] = (uint8_t)trDepth; cu->cbf[0][part + i] = (uint8_t)(singleCbf << trDepth); cu->tskip[0][part + i] = (uint8_t)bestModeId; }
@@ -2292,7 +2318,7 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
       }
     }
   }
-  FCU_SERIAL { g_S.q_dist[LEVEL] += singleDist; g_S.q_cost[LEVEL] += singleCost; g_S.q_frac[LEVEL] += singleFrac; }
+  FCU_SERIAL { g_S.q_dist[LEVEL] += singleDist; g_S.q_cost[LEVEL] += singleCost; g_S.q_frac[LEVEL] += singleFrac; g_S.q_bins[LEVEL] += singleBins; }
 }
 
 /* xSetIntraResultLumaQT, TEncSearch.cpp:1717-1757 (iterative) */
@@ -2818,10 +2844,11 @@ FCU_DEV FCU_NOINLINE void est_intra_pred_luma(CuObj *cu)
   uint32_t overallDistY = 0;
   TU root; tu_root(root, d);
   Yuv *recoT = &G->reco[d][1 - g_S.reco_best_idx[d]];
+  const int keepLuma = initTrDepth == 0;                     /* 2Nx2N: the CU's bits come from the search's coders (check_rd_cost_intra) */
   for (int pu = 0; pu < numPU; pu++) {
     TU tu; if (initTrDepth == 0) tu = root; else tu_child(tu, root, pu, 0);
     const int partOffset = tu.part, N = 1 << tu.log2, log2 = tu.log2;
-    FCU_SERIAL g_S.c64_valid = 0;
+    FCU_SERIAL { g_S.c64_valid = 0; g_S.lf_valid = 0; }
     { FCU_TIC(t_); rmd(cu, tu_key(tu)); FCU_TOC(E, t_, 0); }
     fcu_pu_trace *ptr = FCU_UNI(E.C->pu_trace ? E.C->pu_trace + (size_t)E.cur_ctu * FCU_PUS_PER_CTU + pu_trace_index(d, initTrDepth, cu->zidx + partOffset) : (fcu_pu_trace *)nullptr);
     if (ptr) FCU_SERIAL {                                    /* candidate list and CandCostList as the RMD leaves them */
@@ -2838,26 +2865,33 @@ FCU_DEV FCU_NOINLINE void est_intra_pred_luma(CuObj *cu)
       const int nc = g_S.n_rd;
       for (int m = 0; m < nc; m++) {
         const int orgMode = g_S.rd_mode[m];
-        FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) cu->intra_dir[0][partOffset + i] = (uint8_t)orgMode; cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, d, CI_CURR_BEST), lane); if (lane == 0) { g_S.q_dist[0] = 0; g_S.q_cost[0] = 0; } }
+        FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) cu->intra_dir[0][partOffset + i] = (uint8_t)orgMode; cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, d, CI_CURR_BEST), lane); if (lane == 0) { g_S.q_dist[0] = 0; g_S.q_cost[0] = 0; g_S.q_frac[0] = 0; g_S.q_bins[0] = 0; } }
         recur_luma_qt<0>(cu, tu_key(tu), 1);
         if (g_S.q_cost[0] < g_S.pu_best_cost) {
-          FCU_SERIAL { g_S.pu_best_mode = orgMode; g_S.pu_best_dist = g_S.q_dist[0]; g_S.pu_best_cost = g_S.q_cost[0]; }
+          FCU_SERIAL { g_S.pu_best_mode = orgMode; g_S.pu_best_dist = g_S.q_dist[0]; g_S.pu_best_cost = g_S.q_cost[0]; g_S.lf_frac = (slot_ptr(E, d, CI_CURR_BEST)->frac & 32767) + g_S.q_frac[0]; g_S.lf_bins = g_S.q_bins[0]; g_S.lf_valid = keepLuma; }
           set_intra_result_luma_qt(cu, tu_key(tu), recoT);
-          FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) { G->tmp_tr_idx[i] = cu->tr_idx[partOffset + i]; G->tmp_cbf[i] = cu->cbf[0][partOffset + i]; G->tmp_tskip[i] = cu->tskip[0][partOffset + i]; } }
+          FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) { G->tmp_tr_idx[i] = cu->tr_idx[partOffset + i]; G->tmp_cbf[i] = cu->cbf[0][partOffset + i]; G->tmp_tskip[i] = cu->tskip[0][partOffset + i]; } if (keepLuma) cab_copy(&g_S.cab[CAB_LUMA], &g_S.cab[CAB_GOON], lane); }
         }
       }
+    }
+    if (keepLuma && (singleTU || g_S.n_rd <= 5)) {
+      /* The winner's lane coder is the coder after the walk of the CU's luma encoding, unless the re-run below finds a
+       * cheaper tree: kept for check_rd_cost_intra, out of reach of the tenants of the lane coders (est table, RMD
+       * staging, chroma search). */
+      const int w = CAB_LANE0 + (singleTU ? FCU_UNI((int)g_S.vc_slot[g_S.pu_best_vc]) : FCU_UNI(g_S.pu_best_vc));
+      FCU_FOR_LANES { cab_copy(&g_S.cab[CAB_LUMA], &g_S.cab[w], lane); if (lane == 0) { g_S.lf_frac = g_S.cab[w].frac; g_S.lf_bins = g_S.cab[w].bins; g_S.lf_valid = 1; } }
     }
     /* best mode again with the full RQT (TEncSearch.cpp:2518-2586).  When the TU cannot split the
      * re-run reproduces the first-pass trial exactly (same snapshot, same inputs) and `<` keeps the
      * earlier result, so it is skipped. */
     if (log2 > min_tu_log2_in_cu(d, partSize)) {
       const int orgMode = g_S.pu_best_mode;
-      FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) cu->intra_dir[0][partOffset + i] = (uint8_t)orgMode; cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, d, CI_CURR_BEST), lane); if (lane == 0) { g_S.q_dist[0] = 0; g_S.q_cost[0] = 0; } }
+      FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) cu->intra_dir[0][partOffset + i] = (uint8_t)orgMode; cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, d, CI_CURR_BEST), lane); if (lane == 0) { g_S.q_dist[0] = 0; g_S.q_cost[0] = 0; g_S.q_frac[0] = 0; g_S.q_bins[0] = 0; } }
       { FCU_TIC(t_); recur_luma_qt<0>(cu, tu_key(tu), 0, singleTU ? g_S.pu_best_vc : -1); FCU_TOC(E, t_, 4); }
-      if (g_S.q_cost[0] < g_S.pu_best_cost) {
-        FCU_SERIAL { g_S.pu_best_dist = g_S.q_dist[0]; g_S.pu_best_cost = g_S.q_cost[0]; }
+      if (g_S.q_cost[0] < g_S.pu_best_cost) {                /* the go-on coder is the coder after the walk of the chosen tree, q_frac / q_bins[0] its counts */
+        FCU_SERIAL { g_S.pu_best_dist = g_S.q_dist[0]; g_S.pu_best_cost = g_S.q_cost[0]; g_S.lf_frac = (slot_ptr(E, d, CI_CURR_BEST)->frac & 32767) + g_S.q_frac[0]; g_S.lf_bins = g_S.q_bins[0]; g_S.lf_valid = keepLuma; }
         set_intra_result_luma_qt(cu, tu_key(tu), recoT);
-        FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) { G->tmp_tr_idx[i] = cu->tr_idx[partOffset + i]; G->tmp_cbf[i] = cu->cbf[0][partOffset + i]; G->tmp_tskip[i] = cu->tskip[0][partOffset + i]; } }
+        FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) { G->tmp_tr_idx[i] = cu->tr_idx[partOffset + i]; G->tmp_cbf[i] = cu->cbf[0][partOffset + i]; G->tmp_tskip[i] = cu->tskip[0][partOffset + i]; } if (keepLuma) cab_copy(&g_S.cab[CAB_LUMA], &g_S.cab[CAB_GOON], lane); }
       }
     }
     overallDistY += g_S.pu_best_dist;
@@ -3223,16 +3257,88 @@ FCU_DEV FCU_NOINLINE void check_rd_cost_intra(int d, int partSize)
   }
   { FCU_TIC(t_); est_intra_pred_chroma(cu); FCU_TOC(E, t_, 6); }
   FCU_TIC(t7_);
-  FCU_FOR_LANES {
-    if (lane == 0) {
-      cab_reset_bits((CAB_GOON));
-      encode_cu_syntax(E, (CAB_GOON), cu, 0, d);
-      cu->bits = cab_bits((CAB_GOON)); cu->bins = g_S.cab[CAB_GOON].bins;
-      cu->cost = rd_cost(P, cu->bits, cu->dist);
+#ifdef FCU_PROFILE_CUSYN
+  if (threadIdx.x == 0) g_S.prof_s7 = partSize == SIZE_2Nx2N ? 1 : 2;
+#endif
+  /* The CU's bits (encodeCoeff from [d][CI_CURR_BEST], TEncCu.cpp:1753-1778).  A 2Nx2N CU is not walked again: the luma
+   * search's chosen walk (cab[CAB_LUMA]) and the chroma search's (lane coder 5 + best mode) started from that snapshot too and
+   * have between them pushed every bin of the CU through its context in the order of the final walk -- the two touch
+   * disjoint contexts, a bin's cost depends on its own context only and the Q15 count is additive.  Cb and Cr
+   * share their level contexts and the search codes all Cb leaves before the Cr leaves, so with more than one chroma leaf
+   * the chroma part is walked again, leaf by leaf.  NxN (every PU searched from the snapshot, not from its predecessor's
+   * state) and a CU without a kept luma coder take the full walk. */
+  const int merge = partSize == SIZE_2Nx2N && FCU_UNI(g_S.lf_valid);
+  const int oneLeaf = merge && (FCU_UNI((int)cu->tr_idx[0]) == 0 || d == MAXDEPTH);   /* un-split tree, or four 4x4 luma TUs over one 4x4 chroma block */
+  if (!merge) {
+    FCU_FOR_LANES {
+      if (lane == 0) {
+        cab_reset_bits((CAB_GOON));
+        encode_cu_syntax(E, (CAB_GOON), cu, 0, d);
+        cu->bits = cab_bits((CAB_GOON)); cu->bins = g_S.cab[CAB_GOON].bins;
+        cu->cost = rd_cost(P, cu->bits, cu->dist);
+      }
     }
+    FCU_FOR_LANES cab_copy(slot_ptr(E, d, CI_TEMP_BEST), &g_S.cab[CAB_GOON], lane);
+    FCU_SPATH(E, 2);
+  } else {
+    if (!oneLeaf) {
+      FCU_FOR_LANES {
+        if (lane == 0) {                                     /* the go-on coder is a copy of [d][CI_CURR_BEST] here */
+          cab_reset_bits((CAB_GOON));
+          code_intra_dir_chroma((CAB_GOON), cu->intra_dir[1][0]);
+          TU root; tu_root(root, d);
+          encode_transform((CAB_GOON), cu, 0, tu_key(root), 0);
+        }
+      }
+    }
+    const int cc = oneLeaf ? CAB_LANE0 + 5 + FCU_UNI(g_S.c_best_mode) : (int)CAB_GOON;
+    FCU_FOR_LANES {
+      const Cabac *cur = slot_ptr(E, d, CI_CURR_BEST), *lum = &g_S.cab[CAB_LUMA], *chr = &g_S.cab[cc];
+      Cabac *tmp = slot_ptr(E, d, CI_TEMP_BEST), *go = &g_S.cab[CAB_GOON];
+      if (lane < NCTX / 4) {                                 /* four contexts per lane: luma's byte where luma moved it, chroma's otherwise */
+        const uint32_t k = ((const uint32_t *)cur->ctx)[lane], l = ((const uint32_t *)lum->ctx)[lane], c = ((const uint32_t *)chr->ctx)[lane];
+        uint32_t m = 0;
+        for (int b = 0; b < 32; b += 8) {
+          const uint32_t kb = (k >> b) & 255, lb = (l >> b) & 255, cb = (c >> b) & 255;
+          FCU_CHECK(lb == kb || cb == kb);                   /* no context is moved by both searches */
+          m |= (lb != kb ? lb : cb) << b;
+        }
+        ((uint32_t *)tmp->ctx)[lane] = m; ((uint32_t *)go->ctx)[lane] = m;
+      } else if (lane == NCTX / 4) {
+        const uint64_t f = g_S.lf_frac + chr->frac - (cur->frac & 32767);
+        const uint32_t nb = g_S.lf_bins + chr->bins;
+        tmp->frac = f; tmp->bins = nb; tmp->pad_ = 0; go->frac = f; go->bins = nb; go->pad_ = 0;
+        cu->bits = (uint32_t)(f >> 15); cu->bins = nb;
+        cu->cost = rd_cost(P, cu->bits, cu->dist);
+      }
+    }
+    FCU_SPATH(E, oneLeaf ? 0 : 1);
+#ifdef FCU_EMU
+    g_emu_cu_paths[oneLeaf ? 0 : 1]++;
+#ifdef FCU_EMU_CHECK_CU_MERGE
+    FCU_FOR_LANES {                                          /* the full walk on a spare lane coder must give the merged state */
+      if (lane == 0) {
+        const int w = CAB_LANE0 + MAXLC - 1;
+        cab_copy1(&g_S.cab[w], slot_ptr(E, d, CI_CURR_BEST)); cab_reset_bits(w);
+        encode_cu_syntax(E, w, cu, 0, d);
+        const Cabac *tmp = slot_ptr(E, d, CI_TEMP_BEST);
+        FCU_CHECK(memcmp(g_S.cab[w].ctx, tmp->ctx, NCTX) == 0);
+        FCU_CHECK(g_S.cab[w].frac == tmp->frac); FCU_CHECK(g_S.cab[w].bins == tmp->bins);
+        FCU_CHECK(cab_bits(w) == cu->bits); FCU_CHECK(g_S.cab[w].bins == cu->bins);
+        FCU_CHECK(memcmp(&g_S.cab[CAB_GOON], tmp, sizeof(Cabac)) == 0);
+      }
+    }
+#endif
+#endif
   }
-  FCU_FOR_LANES cab_copy(slot_ptr(E, d, CI_TEMP_BEST), &g_S.cab[CAB_GOON], lane);
+#ifdef FCU_EMU
+  if (!merge) g_emu_cu_paths[2]++;
+#endif
+#ifdef FCU_PROFILE_CUSYN
+  if (threadIdx.x == 0) g_S.prof_s7 = 0;
+#endif
   FCU_TOC(E, t7_, 7);
+  FCU_STOC(E, t7_, partSize == SIZE_2Nx2N ? 11 : 12);
   check_best_mode(d);
 }
 
