@@ -288,9 +288,11 @@ struct Chain {
   const uint8_t *refs[FCU_MAX_REF][3];
   int n_ref, poc, ref_poc[FCU_MAX_REF], col_poc, col_ref_poc[FCU_MAX_REF];
   int int_mv_r[FCU_MAX_REF][2];
-  /* WaveFrontSynchro row chain (fcu_wpp_begin / fcu_wpp_begin_p), written by the host only: wpp = 1 binds the chain to one CTU
-   * row of a one-slice picture, wpp_above = chain index of the row above (-1 for row 0), wpp_sync_in / wpp_sync_out = the sync
-   * slots (NCTX context bytes, m_entropyCodingSyncContextState) of the row above / of this row.  The slots themselves are device
+  /* WaveFrontSynchro row chain (fcu_wpp_begin / fcu_wpp_begin_p / fcu_wpp_begin_slices), written by the host only: wpp = 1 binds
+   * the chain to one CTU row of a picture, wpp_above = chain index of the row above, or -1 for a row that starts a slice (row 0;
+   * with slices of whole rows, p.slice_ctus = R * w_ctu, every R-th row): such a row waits for nothing, loads no contexts and
+   * inherits no search state.  wpp_sync_in / wpp_sync_out = the sync slots (NCTX context bytes,
+   * m_entropyCodingSyncContextState) of the row above (null with wpp_above -1, never read then) / of this row.  The slots themselves are device
    * memory of the context (fcu_kernels.hip), not part of the descriptor: no host copy of the descriptor ever overwrites them. */
   int wpp, wpp_above;
   const uint8_t *wpp_sync_in;
@@ -3597,10 +3599,13 @@ FCU_DEV void load_hot_tables()
 }
 
 /* ---- one CTU of one chain: the loop body of TEncSlice::compressSlice, TEncSlice.cpp:1380-1551.
- * WPP = a WaveFrontSynchro row chain (Chain::wpp): the first CTU of a row below the first restarts the coder (resetEntropy) and,
+ * WPP = a WaveFrontSynchro row chain (Chain::wpp): the first CTU of a row that does not start a slice restarts the coder (resetEntropy) and,
  * when the picture is at least two CTUs wide, takes the contexts saved after the second CTU of the row above (loadContexts of
  * m_entropyCodingSyncContextState, TEncSlice.cpp:1396-1411: contexts only, the Q15 counter stays as the reset leaves it); after
- * the second CTU of its own row it saves its contexts for the row below (:1514-1517).  WPP = false is the plain chain. */
+ * the second CTU of its own row it saves its contexts for the row below (:1514-1517).  A row that starts a slice (slices of whole
+ * rows, fcu_wpp_begin_slices) is the first CTU of its slice: the slice's reset alone, row_start false, wpp_sync_in never read
+ * (CUIsFromSameSliceAndTile(pCtuTR) fails at :1400, nothing is loaded); its above neighbours are masked by E.slice_start.  Every
+ * row saves after its second CTU, whether or not a row of its slice follows.  WPP = false is the plain chain. */
 template <bool WPP = false>
 FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
 {
@@ -3659,7 +3664,11 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
   FCU_TOC(E, t10_, 10);
 }
 
-/* ---- WaveFrontSynchro: one CTU row of a one-slice I picture as a chain (TEncSlice.cpp:1386-1411,1514-1517) ---------------
+/* ---- WaveFrontSynchro: one CTU row of a picture as a chain (TEncSlice.cpp:1386-1411,1514-1517) --------------------------
+ * "The row above" below = the row above IN THE SAME SLICE.  A one-slice picture has one for every row but row 0; a picture cut
+ * into slices of R whole rows (SliceMode 1 with WaveFrontSynchro, fcu_wpp_begin_slices) has none for rows 0, R, 2R, ...: those
+ * are bound with wpp_above -1 and run like a row 0, so no chain ever waits on a chain of another slice, and the critical path of
+ * W x H CTUs falls from W + 2(H - 1) to W + 2(R - 1) CTUs.
  * Row r may decide CTU x once row r-1 has finished CTU min(x + 1, W - 1): that completes every neighbour CTU x reads (left,
  * above-left, above, above-right) and, for x == 0, the sync slot written after CTU 1 of the row above.  The rows of a picture
  * hand these bytes (fcu_ctu_out entries, reconstruction rows, the sync slot) over through per-chain progress words:
@@ -3721,7 +3730,10 @@ FCU_DEV void wpp_publish(unsigned *ctl_, int chain, unsigned done)
  *     [0, n_ref) iff TZ search and a full first CTU; a boundary-first row already holds every slot), so each row chain ends
  *     with HM's state after its row, the last one with HM's state after the picture.
  * The row above is finished when either copy happens (progress W, waited for before the first / the last CTU); its own end copy
- * precedes its last publish.  Lane-indexed loads (vector memory, never the scalar cache: Guideline 16 Pitfall 6). */
+ * precedes its last publish.  Lane-indexed loads (vector memory, never the scalar cache: Guideline 16 Pitfall 6).
+ * Slices of whole rows: "the first row" reads "the first row of the slice" throughout.  A row that starts a slice takes nothing
+ * from the chain before it, at its start or at its end: it begins from its own descriptor (zero after binding: the convention
+ * for slices decided side by side), so the last row chain of a slice ends with the state after that slice. */
 FCU_DEV void wpp_take_search_state(Chain *C, const Chain *A, int first, int end)
 {
   FCU_FOR_LANES {
@@ -3741,12 +3753,12 @@ FCU_DEV FCU_NOINLINE int run_wpp_chain(Chain *C, Scratch *G, unsigned *ctl, int 
   load_hot_tables();
   const int above = FCU_UNI(C->wpp_above), W = FCU_UNI(C->w_ctu), end = FCU_UNI(C->end_ctu);
   const int first = FCU_UNI(C->next_ctu);
-  /* P row below the first: the row above's descriptor (rows of a picture are consecutive chains) and the hand-off rule above */
+  /* P row below the first of its slice: the row above's descriptor (rows of a picture are consecutive chains) and the hand-off rule above */
   const bool inherit = above >= 0 && C->p.slice_type == SLICE_P;
   const Chain *A = C + (above - chain);
   const bool tz = C->p.fast_search != 0, full_first = C->p.width >= CTU && (first / W + 1) * CTU <= C->p.height;
 #ifdef FCU_EMU
-  if (above >= 0) C->wpp_mv_known = 0;
+  if (above >= 0) C->wpp_mv_known = 0;                       /* (a row that starts a slice keeps what its binder declared known) */
 #endif
   if (inherit && tz && !full_first && first < end) {
     if (!wpp_wait(ctl, above, (unsigned)W)) return 0;

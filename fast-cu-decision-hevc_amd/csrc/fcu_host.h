@@ -78,4 +78,29 @@ inline void ldp_slice(fcu_frame_params &fp, int base_qp, int poc)
   fp.slice_type = FCU_SLICE_P; fp.qp = qp; fp.lambda = lambda;
 }
 
+/* ---- WaveFrontSynchro on pictures cut into slices of whole CTU rows (fcu_wpp_begin_slices): the rules of the binding,
+ * shared by libfcu.so and the test-only emulator driver.
+ * wpp_slice_ctus: SliceArgument of a picture W CTUs wide whose slices hold slice_rows rows; fp_slice_ctus, what the caller's
+ * frame parameters name, must be 0 or exactly that (a slice that starts mid-row is not supported).  -1 = invalid. */
+inline int wpp_slice_ctus(int W, int slice_rows, int fp_slice_ctus)
+{
+  if (W < 1 || slice_rows < 1 || (long long)slice_rows * W > 0x7fffffffll) return -1;
+  const int sl = slice_rows * W;
+  return (fp_slice_ctus == 0 || fp_slice_ctus == sl) ? sl : -1;
+}
+/* row (of the picture) that row r waits for and loads its contexts from: r - 1, or -1 for a row that starts a slice -- row 0,
+ * and with slice_rows >= 1 every slice_rows-th row.  slice_rows 0 = one slice. */
+inline int wpp_row_above(int r, int slice_rows) { return (r == 0 || (slice_rows > 0 && r % slice_rows == 0)) ? -1 : r - 1; }
+/* the WPP part of the descriptor of row r of a picture W CTUs wide whose rows are chains [first_chain, ...): its CTU range, the
+ * chain it waits on and the sync slots (`sync` = slot 0 of the context's slot array, one slot of WPP_SYNC_BYTES per chain).
+ * The one place that fills these fields, for libfcu.so's binder and for the emulator driver of the sliced pictures alike. */
+inline void wpp_bind_row(Chain &h, int r, int W, int slice_rows, int first_chain, uint8_t *sync)
+{
+  const int ra = wpp_row_above(r, slice_rows);
+  h.next_ctu = r * W; h.end_ctu = (r + 1) * W;
+  h.wpp = 1; h.wpp_above = ra >= 0 ? first_chain + ra : -1;
+  h.wpp_sync_in = ra >= 0 ? sync + (size_t)WPP_SYNC_BYTES * (first_chain + ra) : nullptr;
+  h.wpp_sync_out = sync + (size_t)WPP_SYNC_BYTES * (first_chain + r);
+}
+
 } // namespace fcu

@@ -343,12 +343,23 @@ int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream
 
 int fcu_wpp_rows(const fcu_ctx *c) { return c ? (c->sp.height + 63) / 64 : 0; }
 
-/* the binding both WPP entry points share: `name` for the messages, the slice type already checked by the caller */
-static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, const char *name,
+/* the binding the WPP entry points share: `name` for the messages, the slice type already checked by the caller.  slice_rows
+ * 0 = a one-slice picture (fp->slice_ctus must be 0); slice_rows R >= 1 (fcu_wpp_begin_slices) = slices of R whole CTU rows.
+ * A row that starts a slice is bound as a row 0 is: no row above (wpp_above -1) and no sync slot to read, so run_wpp_chain
+ * waits for nothing and inherits nothing on it, and compress_ctu resets its coder as the first CTU of a slice (fcu_host.h). */
+static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp_in, const char *name, int slice_rows,
                     const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": WaveFrontSynchro needs one slice per picture (slice_ctus 0)");
   const int rows = fcu_wpp_rows(c), W = (c->sp.width + 63) / 64;
+  fcu_frame_params fp_sliced = *fp_in;
+  const fcu_frame_params *fp = fp_in;
+  if (slice_rows == 0) {
+    if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": WaveFrontSynchro needs one slice per picture (slice_ctus 0); slices of whole CTU rows are bound by fcu_wpp_begin_slices");
+  } else {
+    const int sl = wpp_slice_ctus(W, slice_rows, fp->slice_ctus);
+    if (sl < 0) return fail(FCU_ERR_ARG, std::string(name) + ": slice_rows must be >= 1 and slice_ctus 0 or slice_rows x the picture width in CTUs (a slice starts at a row start)");
+    fp_sliced.slice_ctus = sl; fp = &fp_sliced;
+  }
   if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains for one chain per CTU row (fcu_wpp_rows)");
   if (!c->d_wpp_ctl) {
     const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
@@ -365,10 +376,7 @@ static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, con
   for (int r = 0; r < rows; r++) {
     Chain &h = c->h_chains[(size_t)(first_chain + r)];
     h = base;
-    h.next_ctu = r * W; h.end_ctu = (r + 1) * W;
-    h.wpp = 1; h.wpp_above = r ? first_chain + r - 1 : -1;
-    h.wpp_sync_in = r ? c->d_wpp_sync + (size_t)WPP_SYNC_BYTES * (first_chain + r - 1) : nullptr;
-    h.wpp_sync_out = c->d_wpp_sync + (size_t)WPP_SYNC_BYTES * (first_chain + r);
+    wpp_bind_row(h, r, W, slice_rows, first_chain, c->d_wpp_sync);
     c->h_pos[(size_t)(first_chain + r)] = r * W;
   }
   HIPCHK(hipMemcpy(&c->d_chains[first_chain], &c->h_chains[(size_t)first_chain], sizeof(Chain) * (size_t)rows, hipMemcpyHostToDevice));
@@ -380,7 +388,7 @@ int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
 {
   if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin: bad argument");
   if (fp->slice_type != FCU_SLICE_I) return fail(FCU_ERR_ARG, "fcu_wpp_begin: binds I slices only (P slices: fcu_wpp_begin_p)");
-  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin", oy, ou, ov, ry, ru, rv, dev_out);
+  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin", 0, oy, ou, ov, ry, ru, rv, dev_out);
 }
 
 int fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
@@ -388,10 +396,18 @@ int fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
 {
   if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: bad argument");
   if (fp->slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: binds P slices only (I slices: fcu_wpp_begin)");
-  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_p", oy, ou, ov, ry, ru, rv, dev_out);
+  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_p", 0, oy, ou, ov, ry, ru, rv, dev_out);
 }
 
-/* the rows of a P picture decide one slice: every row must name row 0's reference pictures and collocated field */
+int fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int slice_rows,
+                         const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin_slices: bad argument");
+  if (slice_rows < 1) return fail(FCU_ERR_ARG, "fcu_wpp_begin_slices: slice_rows must be at least 1");
+  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_slices", slice_rows, oy, ou, ov, ry, ru, rv, dev_out);     /* the slice type: fcu_chain_begin's check */
+}
+
+/* the rows of a P picture decide one picture: every row must name row 0's reference pictures and collocated field */
 static bool wpp_same_refs(const Chain &a, const Chain &b)
 {
   if (a.n_ref != b.n_ref || a.poc != b.poc || a.col != b.col || a.col_poc != b.col_poc || a.ref_stride[0] != b.ref_stride[0]) return false;
@@ -410,12 +426,21 @@ int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
   if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
   for (int i = first; i < first + n; i++) {
     const Chain &h = c->h_chains[(size_t)i];
-    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin");
-    /* a picture starts with its row 0 (at `first` or right after the last row of the picture before it) and its rows follow */
-    const bool starts_ok = h.wpp_above < 0 ? (i == first || c->h_chains[(size_t)i - 1].end_ctu == c->h_chains[(size_t)i - 1].n_ctu) : (i > first && h.wpp_above == i - 1);
-    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin");
+    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices");
+    /* a picture starts with its row 0 (at `first` or right after the last row of the picture before it) and its rows follow at
+     * consecutive chains; a row without a row above that is not row 0 must be the first row of a slice of whole rows of the
+     * picture the chain before it belongs to (fcu_wpp_begin_slices) */
+    const int row = h.next_ctu / h.w_ctu, slice_rows = h.p.slice_ctus / h.w_ctu;      /* slice_ctus 0 = one slice: slice_rows 0, every row below row 0 has a row above */
+    bool starts_ok;
+    if (row == 0) starts_ok = h.wpp_above < 0 && (i == first || c->h_chains[(size_t)i - 1].end_ctu == c->h_chains[(size_t)i - 1].n_ctu);
+    else {
+      const int ra = wpp_row_above(row, slice_rows);
+      const Chain *b = i > first ? &c->h_chains[(size_t)i - 1] : nullptr;
+      starts_ok = b && b->out == h.out && b->end_ctu == h.next_ctu && b->p.slice_ctus == h.p.slice_ctus && h.wpp_above == (ra >= 0 ? i - 1 : -1);
+    }
+    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices, their rows at consecutive chains");
     if (i == first + n - 1 && h.end_ctu != h.n_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture");
-    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin)");
+    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin(_p) / fcu_wpp_begin_slices)");
     if (h.p.slice_type == SLICE_P) {
       if (h.ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_wpp: P row without reference picture (fcu_chain_set_reference(s) on every row)");
       const Chain &row0 = c->h_chains[(size_t)(i - (h.next_ctu / h.w_ctu))];

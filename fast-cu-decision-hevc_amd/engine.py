@@ -87,7 +87,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_build_info", "fcu_abi_sizeof", "fcu_tcm_threshold", "fcu_chain_set_reference", "fcu_pad_reference", "fcu_pad_sizes", "fcu_ldp_slice", "fcu_get_ctx_state_full",
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
-           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p"]
+           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -168,6 +168,7 @@ def load_lib():
     lib.fcu_wpp_rows.argtypes = [C.c_void_p]
     lib.fcu_wpp_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
     lib.fcu_wpp_begin_p.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
+    lib.fcu_wpp_begin_slices.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int] + [C.c_void_p] * 7
     lib.fcu_compress_wpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib
@@ -364,14 +365,17 @@ class CuEngine:
         return n_sl, rec, out
 
     def init_wpp_picture(self, first_chain, org, qp, rec=None, out=None, params=None, ref=None, refs=None, ref_pocs=None, poc=None,
-                         col_ref_pocs=None, col=None, search_state=None, **flags):
+                         col_ref_pocs=None, col=None, search_state=None, slice_rows=None, **flags):
         """One picture, one slice, WaveFrontSynchro on: chains [first_chain, first_chain + n_rows) become its CTU rows, top to
         bottom; they share the picture's planes and fcu_ctu_out array.  params / flags: the frame parameters as init_chain takes
         them (I-slice defaults for `qp` without params).  An I slice binds with fcu_wpp_begin; a P slice (params.slice_type P)
         with fcu_wpp_begin_p, and then takes ref or refs / ref_pocs / poc / col_ref_pocs and col (init_chain) on every row and
         search_state (set_search_state: what the previous picture left; zero when None) on row 0.  set_decision rewrites the
         search state: a caller that sets decision states passes search_state=None and calls set_search_state(first_chain, ...)
-        after its set_decision calls.  Returns (n_rows, rec, out)."""
+        after its set_decision calls.
+        slice_rows: WaveFrontSynchro with SliceMode 1 -- the picture is cut into independent slices of slice_rows whole CTU
+        rows (fcu_wpp_begin_slices, I or P by params.slice_type): the first row of every slice waits for nothing and starts from
+        a zero search state; search_state, if given, goes to row 0 (the first slice) only.  Returns (n_rows, rec, out)."""
         if refs is not None:
             assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
         torch = self.torch
@@ -392,8 +396,12 @@ class CuEngine:
                 raise TypeError(f"init_wpp_picture: unknown frame parameter {k!r}")
             setattr(fp, k, v)
         p_slice = fp.slice_type == SLICE_P
-        begin, name = (self.lib.fcu_wpp_begin_p, "fcu_wpp_begin_p") if p_slice else (self.lib.fcu_wpp_begin, "fcu_wpp_begin")
-        self._chk(begin(self.h, first_chain, C.byref(fp), *[p.data_ptr() for p in planes], *[p.data_ptr() for p in rec], out.data_ptr()), name)
+        ptrs = [p.data_ptr() for p in planes] + [p.data_ptr() for p in rec] + [out.data_ptr()]
+        if slice_rows is not None:
+            self._chk(self.lib.fcu_wpp_begin_slices(self.h, first_chain, C.byref(fp), int(slice_rows), *ptrs), "fcu_wpp_begin_slices")
+        else:
+            begin, name = (self.lib.fcu_wpp_begin_p, "fcu_wpp_begin_p") if p_slice else (self.lib.fcu_wpp_begin, "fcu_wpp_begin")
+            self._chk(begin(self.h, first_chain, C.byref(fp), *ptrs), name)
         n_rows = self.lib.fcu_wpp_rows(self.h)
         for r in range(n_rows):
             self._keep[first_chain + r] = (planes, rec, out)

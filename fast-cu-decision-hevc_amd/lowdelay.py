@@ -20,6 +20,11 @@ for a slice whose first CTU is too small for a 64x64 CU (fcu_chain_
 HM's value).  With WPP the launch hands it from row to row exactly, and the driver carries it from picture to picture as HM
 does: the last row chain's state becomes the next picture's row-0 state.
 
+WaveFrontSynchro with SliceMode 1 (wpp=True, slice_rows=N): every picture is cut into independent slices of N whole CTU rows
+whose rows are chains (fcu_wpp_begin_slices); the first row of a slice waits for nothing.  The slices are decided side by side,
+so, as for the slice chains above, every slice of every picture starts the TZ search state from zero and nothing is carried from
+picture to picture; SAO is told the slice length (merge candidates do not cross slices).
+
 Context-table choice of a P picture (cabac_init_flag): HM initialises a P slice from the B-slice tables when
 TEncSbac::determineCabacInitIdx picked them after the previous slice (TEncSlice.cpp:1750-1753).  That choice is made on the
 BITSTREAM coder's final state, which includes the SAO syntax and a per-context "bins were coded" flag the RD path does not
@@ -51,16 +56,23 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above)."""
         if wpp and slice_ctus:
-            raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None)")
-        self.wpp = wpp
+            raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
+        if slice_rows is not None and not wpp:
+            raise ValueError("LowDelayPDecider: slice_rows cuts a WaveFrontSynchro picture into slices of whole CTU rows and needs wpp=True (without WPP: slice_ctus)")
+        if slice_rows is not None and slice_rows < 1:
+            raise ValueError("LowDelayPDecider: slice_rows must be at least 1")
+        self.wpp, self.slice_rows = wpp, slice_rows
         self.width, self.height, self.base_qp, self.n_clips, self.search_range = width, height, base_qp, n_clips, search_range
         n_ctu = ((width + 63) // 64) * ((height + 63) // 64)
         self.slice_ctus = slice_ctus if slice_ctus else n_ctu
         self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
+        self.sao_slice_ctus = self.slice_ctus if self.n_slices > 1 else 0      # what fcu_sao is told
+        if slice_rows is not None:
+            self.sao_slice_ctus = slice_rows * ((width + 63) // 64)
         self.n_chains = (height + 63) // 64 if wpp else self.n_slices          # chains per picture: rows (WPP) or slices
         self.search_state = [None] * n_clips             # WPP: m_integerMv2Nx2N after each clip's last picture
         self.eng = _engine.CuEngine(width, height, max_chains=n_clips * self.n_chains, device=device)
@@ -103,8 +115,8 @@ class LowDelayPDecider:
             if ref is not None and self.n_refs > 1:
                 kw = dict(refs=[self.dpb[s][q][0] for q in rl], ref_pocs=rl, poc=poc, col_ref_pocs=self.dpb[s][rl[0]][1])
             if self.wpp:
-                state = self.search_state[s] if fp.slice_type == _engine.SLICE_P else None
-                _, rec, out = eng.init_wpp_picture(first, f, fp.qp, params=fp, col=col, search_state=state, **kw)
+                state = self.search_state[s] if (fp.slice_type == _engine.SLICE_P and self.slice_rows is None) else None
+                _, rec, out = eng.init_wpp_picture(first, f, fp.qp, params=fp, col=col, search_state=state, slice_rows=self.slice_rows, **kw)
                 res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
                 continue
             rec, out = eng.init_chain(first, f, fp.qp, slice_ctus=self.slice_ctus if self.n_slices > 1 else 0, params=fp, col=col, **kw)
@@ -119,7 +131,8 @@ class LowDelayPDecider:
         if self.wpp:
             eng.compress_wpp(0, self.n_clips * self.n_chains)
             for s, r in enumerate(res):                      # HM's state after the picture: the last row's (fcu_wpp_begin_p)
-                r["search_state"] = self.search_state[s] = eng.search_state(r["first"] + self.n_chains - 1)
+                r["search_state"] = eng.search_state(r["first"] + self.n_chains - 1)      # (sliced: the state after the last slice)
+                self.search_state[s] = r["search_state"] if self.slice_rows is None else None
         else:
             eng.compress_chains(0, self.n_clips * self.n_slices, self.slice_ctus)
         for s, r in enumerate(res):
@@ -129,7 +142,7 @@ class LowDelayPDecider:
         if self.do_sao:
             layer = _engine.ldp_layer(poc)
             pics = [{"org": eng._keep[r["first"]][0], "rec": r["rec"], "qp": fp.qp, "lambda_": fp.lambda_, "slice_type": fp.slice_type,
-                     "slice_ctus": self.slice_ctus if self.n_slices > 1 else 0, "enabled": self.sao_rate[s].enabled(layer)} for s, r in enumerate(res)]
+                     "slice_ctus": self.sao_slice_ctus, "enabled": self.sao_rate[s].enabled(layer)} for s, r in enumerate(res)]
             coded, off, _ = eng.sao(pics)
             for s, r in enumerate(res):
                 r["sao"], r["sao_enabled"] = coded[s], pics[s]["enabled"]

@@ -78,16 +78,23 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
         run as concurrent chains, but every slice start cuts the intra neighbourhood and resets CABAC.
         wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains, each row waiting for the row above
-        (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.  Cannot be combined with slice_ctus."""
+        (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.  Cannot be combined with slice_ctus.
+        slice_rows (with wpp only): WaveFrontSynchro together with SliceMode 1, SliceArgument = slice_rows x the picture width in
+        CTUs -- independent slices of slice_rows whole CTU rows whose rows run as chains (fcu_wpp_begin_slices): the first row of
+        a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1)."""
         if wpp and slice_ctus:
-            raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None)")
-        self.wpp = wpp
+            raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
+        if slice_rows is not None and not wpp:
+            raise ValueError("SequenceDecider: slice_rows cuts a WaveFrontSynchro picture into slices of whole CTU rows and needs wpp=True (without WPP: slice_ctus)")
+        if slice_rows is not None and slice_rows < 1:
+            raise ValueError("SequenceDecider: slice_rows must be at least 1")
+        self.wpp, self.slice_rows = wpp, slice_rows
         self.width, self.height, self.qp, self.fast, self.do_deblock, self.flags = width, height, qp, fast, deblock, flags
         self.in_flight = max(1, in_flight)
         w_ctu = (width + 63) // 64
@@ -96,6 +103,8 @@ class SequenceDecider:
         self.slice_mode = "SliceMode 0 (one slice per picture)" if self.slice_ctus >= n_ctu else f"SliceMode 1, SliceArgument {self.slice_ctus}"
         self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
         if wpp:
+            if slice_rows is not None:
+                self.slice_mode = f"SliceMode 1, SliceArgument {slice_rows * w_ctu}"
             self.slice_mode += ", WaveFrontSynchro"
             self.n_slices = (height + 63) // 64                 # chains per picture: one per CTU row
         self.eng = _engine.CuEngine(width, height, max_chains=self.n_slices * self.in_flight, device=device)
@@ -127,7 +136,7 @@ class SequenceDecider:
             state, sk, te = self.schedule.begin_picture(poc) if self.fast else (TRAINING, np.zeros(4, np.uint8), np.zeros(4, np.uint8))
             first = i * self.n_slices
             if self.wpp:
-                n_sl, rec, out = eng.init_wpp_picture(first, yuv, self.qp, **self.flags)
+                n_sl, rec, out = eng.init_wpp_picture(first, yuv, self.qp, slice_rows=self.slice_rows, **self.flags)
             else:
                 n_sl, rec, out = eng.init_slice_chains(first, yuv, self.qp, self.slice_ctus, **self.flags)
             if state != TRAINING:

@@ -179,7 +179,8 @@ int  fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_strea
  * fcu_wpp_begin binds chains [first_chain, first_chain + fcu_wpp_rows(c)) to the CTU rows of ONE I picture, top to bottom (the
  * arguments of fcu_chain_begin; the rows share the planes and dev_out); fp->slice_type must be FCU_SLICE_I.  fcu_wpp_begin_p
  * takes the same arguments for ONE P picture; fp->slice_type must be FCU_SLICE_P.  Both need fp->slice_ctus 0 (WPP with
- * SliceMode 1 is not supported; neither is writing substreams / entry points); otherwise, or with too few chains, FCU_ERR_ARG.
+ * SliceMode 1 goes through fcu_wpp_begin_slices below; writing substreams / entry points is not supported); otherwise, or with
+ * too few chains, FCU_ERR_ARG.
  * P pictures: after fcu_wpp_begin_p, set the reference pictures (fcu_chain_set_reference or _set_references, and
  * _set_collocated_pocs) and the collocated field (fcu_chain_set_collocated) on EVERY row chain, the same on each; set the search
  * state (fcu_chain_set_search_state: what the previous picture left) on ROW 0 only.  Call order per row: fcu_chain_set_decision
@@ -191,7 +192,21 @@ int  fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_strea
  * reads first (its depth-0 2Nx2N searches), so only the partial bottom row, or a picture narrower than 64, waits longer.
  * fcu_chain_set_decision, fcu_chain_set_pu_trace, fcu_get_verify_counts (rows added up in chain order), fcu_chain_position and
  * fcu_get_ctx_state (the state after the chain's row) work on row chains as on slice chains; fcu_compress_chains /
- * fcu_compress_ctu / fcu_chain_set_range on a row chain return FCU_ERR_STATE. */
+ * fcu_compress_ctu / fcu_chain_set_range on a row chain return FCU_ERR_STATE.
+ * WaveFrontSynchro with SliceMode 1: fcu_wpp_begin_slices binds the same fcu_wpp_rows(c) chains to the CTU rows of ONE picture
+ * cut into independent slices of slice_rows whole CTU rows (the last slice holds the rows that are left); fp->slice_type selects
+ * I or P.  slice_rows >= 1; fp->slice_ctus 0 or exactly slice_rows x the picture width in CTUs, which is what the picture is
+ * decided with; anything else (a slice that starts mid-row), or too few chains, FCU_ERR_ARG.  Every slice starts at a row start:
+ *   - the first row of a slice is the first CTU of a slice AND a row start: the slice's reset, nothing loaded (the above-right CTU
+ *     is in another slice), above neighbours unavailable.  It waits for nothing: it depends on nothing the slice above produced;
+ *   - every other row of the slice follows the rules above with "row 0" read as "the first row of my slice";
+ *   - every row saves its contexts after its second CTU.
+ * A picture of W x H CTUs is H chains with a critical path of W + 2(slice_rows - 1) CTUs; slice_rows >= H decides what
+ * fcu_wpp_begin(_p) decides.  P pictures: the setters as for fcu_wpp_begin_p, on every row.  The search state does not cross a
+ * slice boundary: the first row of EVERY slice starts from its own descriptor (zero after binding -- this library's convention
+ * for slices decided side by side -- unless fcu_chain_set_search_state put a state there), and fcu_chain_get_search_state on the
+ * last row chain of a slice returns the state after that slice.  HM's raster walk would carry the state into the next slice;
+ * that differs only for a slice whose first CTU is too small for a 64x64 CU. */
 int  fcu_wpp_rows(const fcu_ctx *c);
 int  fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
                    const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
@@ -199,8 +214,11 @@ int  fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
 int  fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
                      const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
                      uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
+int  fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int slice_rows,
+                          const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
+                          uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
 /* Decide every row chain in [first, first + n) to the end, in one launch on `hip_stream`.  The range must hold whole pictures
- * bound by fcu_wpp_begin(_p) and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin; also for a P
+ * bound by fcu_wpp_begin(_p) or fcu_wpp_begin_slices and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin; also for a P
  * row without a reference picture, or whose references or collocated field differ from its row 0's).  It may hold more
  * chains than the GPU keeps resident.  Returns when the launch has finished; FCU_ERR_STATE if a row gave up waiting for the
  * row above (a bounded wait of 120 s; the pictures of the launch are then undefined). */

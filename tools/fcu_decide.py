@@ -43,14 +43,17 @@ def main():
     ap.add_argument("--slice-ctus", type=int, default=0, help="SliceMode 1: CTUs per slice (default: one slice per picture)")
     ap.add_argument("--row-slices", action="store_true", help="SliceMode 1 with one CTU row per slice")
     ap.add_argument("--wpp", action="store_true", help="WaveFrontSynchro: one slice per picture, its CTU rows decided as chains that wait for the row above")
+    ap.add_argument("--slice-rows", type=int, default=None, help="with --wpp: SliceMode 1 with slices of this many whole CTU rows, the rows of every slice decided as chains")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
+    if args.slice_rows is not None and not args.wpp:
+        ap.error("--slice-rows needs --wpp (without WaveFrontSynchro: --slice-ctus / --row-slices)")
     import __graft_entry__ as g
     pkg = g.load_package()
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
-    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp,
+    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows,
                               schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
