@@ -3,6 +3,8 @@
  * slice with libm (lambda, sqrt(lambda), chroma distortion weight, RDOQ lambdas, RDOQ error
  * scales, sign-hiding rdFactor).  They are handed to the kernels as f64/i64 bit patterns so
  * that no transcendental is ever evaluated on the device.
+ * Also the host-side fills of the chain descriptor (chain_bind ... wpp_bind_row), the one copy
+ * libfcu.so and the test-only emulators bind a chain with.
  */
 #pragma once
 #include <math.h>
@@ -78,6 +80,59 @@ inline void ldp_slice(fcu_frame_params &fp, int base_qp, int poc)
   fp.slice_type = FCU_SLICE_P; fp.qp = qp; fp.lambda = lambda;
 }
 
+/* ---- The host-side fills of the chain descriptor.  Plain pointers in, fields out, no HIP call: the entry points of libfcu.so
+ * (fcu_kernels.hip: the checks, the error texts, the copies to the device) and the test-only emulator drivers (tests/emu, built
+ * with -DFCU_EMU) bind a chain through these functions and through nothing else. */
+
+/* fcu_chain_begin: a zeroed descriptor, the slice's parameters, the planes of a width x height picture and its output array;
+ * the chain's range is the whole picture */
+inline void chain_bind(Chain &h, int width, int height, const fcu_frame_params &fp,
+                       const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *out)
+{
+  memset(&h, 0, sizeof(h));
+  fill_params(h.p, width, height, fp);
+  h.org[0] = oy; h.org[1] = ou; h.org[2] = ov; h.rec[0] = ry; h.rec[1] = ru; h.rec[2] = rv;
+  h.stride[0] = width; h.stride[1] = h.stride[2] = width / 2;
+  h.out = out;
+  h.w_ctu = (width + 63) / 64; h.h_ctu = (height + 63) / 64; h.n_ctu = h.w_ctu * h.h_ctu;
+  h.next_ctu = 0; h.end_ctu = h.n_ctu;
+}
+
+/* list 0 of a bound P chain: pad_planes[3r .. 3r+2] = first byte of the padded Y, U, V planes of RefPicList0[r] (luma border
+ * FCU_REF_MARGIN), ref_pocs[r] their POCs, cur_poc the picture's.  Writes ref / ref_stride, refs[r] and ref_poc[r] for r < n_ref,
+ * n_ref, poc, and the collocated picture = RefPicList0[0] with col_ref_poc[0] = its POC - 1; the slots of col_ref_poc past 0
+ * stay as they are (chain_set_collocated_pocs names them).  fcu_chain_set_reference is the one-picture form: POC 0 seen from
+ * POC 1, so no vector is ever scaled. */
+inline void chain_set_list0(Chain &h, int n_ref, const uint8_t *const *pad_planes, const int *ref_pocs, int cur_poc)
+{
+  const int m = FCU_REF_MARGIN, sy = h.p.width + 2 * m, sc = h.p.width / 2 + m;
+  h.ref_stride[0] = sy; h.ref_stride[1] = h.ref_stride[2] = sc;
+  for (int r = 0; r < n_ref; r++) {
+    h.refs[r][0] = pad_planes[3 * r] + (size_t)m * sy + m;
+    h.refs[r][1] = pad_planes[3 * r + 1] + (size_t)(m / 2) * sc + m / 2; h.refs[r][2] = pad_planes[3 * r + 2] + (size_t)(m / 2) * sc + m / 2;
+    h.ref_poc[r] = ref_pocs[r];
+  }
+  for (int k = 0; k < 3; k++) h.ref[k] = h.refs[0][k];
+  h.n_ref = n_ref; h.poc = cur_poc; h.col_poc = ref_pocs[0]; h.col_ref_poc[0] = ref_pocs[0] - 1;
+}
+
+/* fcu_chain_set_collocated_pocs: the POCs the collocated picture's own list 0 named (slots past n: col_poc - 1).  false = a slot
+ * holds the collocated picture's own POC (the slots before it are written) */
+inline bool chain_set_collocated_pocs(Chain &h, int col_poc, const int *col_ref_pocs, int n)
+{
+  h.col_poc = col_poc;
+  for (int k = 0; k < FCU_MAX_REF; k++) { h.col_ref_poc[k] = k < n ? col_ref_pocs[k] : col_poc - 1; if (h.col_ref_poc[k] == col_poc) return false; }
+  return true;
+}
+
+/* fcu_chain_set_decision: the fork's decision block; the verification counters start from zero */
+inline void chain_set_decision(Chain &h, int state, int depth_exception, const int16_t *obf, const uint8_t *sw_skip, const uint8_t *sw_term)
+{
+  h.dec_state = state; h.depth_exception = depth_exception != 0; h.obf = obf; h.obf_stride = h.p.width / 4;
+  for (int d = 0; d < 4; d++) { h.sw_skip[d] = sw_skip[d] != 0; h.sw_term[d] = sw_term[d] != 0; }
+  memset(h.ver, 0, sizeof(h.ver));
+}
+
 /* ---- WaveFrontSynchro on pictures cut into slices of whole CTU rows (fcu_wpp_begin_slices): the rules of the binding,
  * shared by libfcu.so and the test-only emulator driver.
  * wpp_slice_ctus: SliceArgument of a picture W CTUs wide whose slices hold slice_rows rows; fp_slice_ctus, what the caller's
@@ -93,7 +148,7 @@ inline int wpp_slice_ctus(int W, int slice_rows, int fp_slice_ctus)
 inline int wpp_row_above(int r, int slice_rows) { return (r == 0 || (slice_rows > 0 && r % slice_rows == 0)) ? -1 : r - 1; }
 /* the WPP part of the descriptor of row r of a picture W CTUs wide whose rows are chains [first_chain, ...): its CTU range, the
  * chain it waits on and the sync slots (`sync` = slot 0 of the context's slot array, one slot of WPP_SYNC_BYTES per chain).
- * The one place that fills these fields, for libfcu.so's binder and for the emulator driver of the sliced pictures alike. */
+ * The one place that fills these fields, for libfcu.so's binder and for the emulator driver (tests/emu/wpp_emu.cpp) alike. */
 inline void wpp_bind_row(Chain &h, int r, int W, int slice_rows, int first_chain, uint8_t *sync)
 {
   const int ra = wpp_row_above(r, slice_rows);

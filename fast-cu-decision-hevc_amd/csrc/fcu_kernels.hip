@@ -190,13 +190,7 @@ int fcu_chain_begin(fcu_ctx *c, int chain, const fcu_frame_params *fp,
   if (fp->slice_type == FCU_SLICE_P && (!(fp->lambda > 0.0) || fp->search_range < 1 || fp->search_range > 64)) return fail(FCU_ERR_ARG, "fcu_chain_begin: a P slice needs its lambda (fcu_ldp_slice) and 1 <= search_range <= 64");
   HIPCHK(hipSetDevice(c->sp.device));
   Chain &h = c->h_chains[(size_t)chain];
-  memset(&h, 0, sizeof(h));
-  fill_params(h.p, c->sp.width, c->sp.height, *fp);
-  h.org[0] = oy; h.org[1] = ou; h.org[2] = ov; h.rec[0] = ry; h.rec[1] = ru; h.rec[2] = rv;
-  h.stride[0] = c->sp.width; h.stride[1] = h.stride[2] = c->sp.width / 2;
-  h.out = dev_out;
-  h.w_ctu = (c->sp.width + 63) / 64; h.h_ctu = (c->sp.height + 63) / 64; h.n_ctu = h.w_ctu * h.h_ctu;
-  h.next_ctu = 0; h.end_ctu = h.n_ctu;
+  chain_bind(h, c->sp.width, c->sp.height, *fp, oy, ou, ov, ry, ru, rv, dev_out);
   c->h_pos[(size_t)chain] = 0;
   HIPCHK(hipMemcpy(&c->d_chains[chain], &h, sizeof(Chain), hipMemcpyHostToDevice));
   return FCU_OK;
@@ -233,13 +227,11 @@ int fcu_chain_set_reference(fcu_ctx *c, int chain, const uint8_t *py, const uint
   Chain &h = c->h_chains[(size_t)chain];
   if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_reference: chain not bound (fcu_chain_begin)");
   HIPCHK(hipSetDevice(c->sp.device));
-  const int m = FCU_REF_MARGIN, sy = c->sp.width + 2 * m, sc = c->sp.width / 2 + m;
-  h.ref_stride[0] = sy; h.ref_stride[1] = h.ref_stride[2] = sc;
-  h.ref[0] = py + (size_t)m * sy + m; h.ref[1] = pu + (size_t)(m / 2) * sc + m / 2; h.ref[2] = pv + (size_t)(m / 2) * sc + m / 2;
   static_assert(offsetof(Chain, ref_stride) == offsetof(Chain, ref) + 3 * sizeof(void *), "ref / ref_stride are adjacent");
   /* this entry point: one reference picture at POC distance 1 (no vector is ever scaled), list 0 = { this picture } */
-  for (int k = 0; k < 3; k++) h.refs[0][k] = h.ref[k];
-  h.n_ref = 1; h.poc = 1; h.ref_poc[0] = 0; h.col_poc = 0; h.col_ref_poc[0] = -1;
+  const uint8_t *const planes[3] = { py, pu, pv };
+  const int ref_poc = 0;
+  chain_set_list0(h, 1, planes, &ref_poc, 1);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, ref), &h.ref[0], 3 * sizeof(void *) + 3 * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
@@ -255,13 +247,7 @@ int fcu_chain_set_references(fcu_ctx *c, int chain, int n_ref, const uint8_t *co
   int rc = fcu_chain_set_reference(c, chain, dev_pad_planes[0], dev_pad_planes[1], dev_pad_planes[2]);
   if (rc != FCU_OK) return rc;
   Chain &h = c->h_chains[(size_t)chain];
-  const int m = FCU_REF_MARGIN, sy = c->sp.width + 2 * m, sc = c->sp.width / 2 + m;
-  for (int r = 0; r < n_ref; r++) {
-    h.refs[r][0] = dev_pad_planes[3 * r] + (size_t)m * sy + m;
-    h.refs[r][1] = dev_pad_planes[3 * r + 1] + (size_t)(m / 2) * sc + m / 2; h.refs[r][2] = dev_pad_planes[3 * r + 2] + (size_t)(m / 2) * sc + m / 2;
-    h.ref_poc[r] = ref_pocs[r];
-  }
-  h.n_ref = n_ref; h.poc = cur_poc; h.col_poc = ref_pocs[0]; h.col_ref_poc[0] = ref_pocs[0] - 1;
+  chain_set_list0(h, n_ref, dev_pad_planes, ref_pocs, cur_poc);       /* (ref / ref_stride: the values the call above has copied) */
   HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
   return FCU_OK;
 }
@@ -291,8 +277,7 @@ int fcu_chain_set_collocated_pocs(fcu_ctx *c, int chain, int col_poc, const int 
   Chain &h = c->h_chains[(size_t)chain];
   if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_collocated_pocs: chain not bound (fcu_chain_begin)");
   HIPCHK(hipSetDevice(c->sp.device));
-  h.col_poc = col_poc;
-  for (int k = 0; k < FCU_MAX_REF; k++) { h.col_ref_poc[k] = k < n ? col_ref_pocs[k] : col_poc - 1; if (h.col_ref_poc[k] == col_poc) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: a reference of the collocated picture has its own POC"); }
+  if (!chain_set_collocated_pocs(h, col_poc, col_ref_pocs, n)) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: a reference of the collocated picture has its own POC");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
   return FCU_OK;
@@ -548,9 +533,7 @@ int fcu_chain_set_decision(fcu_ctx *c, int chain, const fcu_decision_params *dp)
   Chain &h = c->h_chains[(size_t)chain];
   if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_decision: chain not bound (fcu_chain_begin)");
   HIPCHK(hipSetDevice(c->sp.device));
-  h.dec_state = dp->state; h.depth_exception = dp->depth_exception != 0; h.obf = dp->dev_obf; h.obf_stride = c->sp.width / 4;
-  for (int d = 0; d < 4; d++) { h.sw_skip[d] = dp->sw_skip2nx2n[d] != 0; h.sw_term[d] = dp->sw_terminate[d] != 0; }
-  memset(h.ver, 0, sizeof(h.ver));
+  chain_set_decision(h, dp->state, dp->depth_exception, dp->dev_obf, dp->sw_skip2nx2n, dp->sw_terminate);
   /* only the decision block of the descriptor: the chain's position and context state on the device stay as they are */
   const size_t off = offsetof(Chain, dec_state);
   HIPCHK(hipDeviceSynchronize());

@@ -19,14 +19,9 @@ void *fcu_emu_create(int width, int height, int qp, int slice_ctus, int tools, c
                      uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *out)
 {
   EmuChain *e = new EmuChain();
-  memset(&e->c, 0, sizeof(e->c));
   fcu_frame_params fp; default_frame_params(fp, qp); fp.slice_ctus = slice_ctus;
   if (tools >= 0) { fp.transform_skip = tools & 1; fp.transform_skip_fast = (tools >> 1) & 1; fp.sign_hiding = (tools >> 2) & 1; fp.strong_intra_smoothing = (tools >> 3) & 1; }
-  fill_params(e->c.p, width, height, fp);
-  e->c.org[0] = oy; e->c.org[1] = ou; e->c.org[2] = ov; e->c.rec[0] = ry; e->c.rec[1] = ru; e->c.rec[2] = rv;
-  e->c.stride[0] = width; e->c.stride[1] = e->c.stride[2] = width / 2;
-  e->c.out = out;
-  e->c.w_ctu = (width + 63) / 64; e->c.h_ctu = (height + 63) / 64; e->c.n_ctu = e->c.w_ctu * e->c.h_ctu;
+  chain_bind(e->c, width, height, fp, oy, ou, ov, ry, ru, rv, out);      /* the fill of fcu_chain_begin */
   load_hot_tables();
   e->g = (Scratch *)calloc(1, sizeof(Scratch));
   return e;
@@ -40,23 +35,16 @@ void fcu_emu_set_p(void *h, int qp, double lambda, int search_range, int fast_se
   fcu_frame_params fp; default_frame_params(fp, qp);
   fp.slice_ctus = e->c.p.slice_ctus; fp.slice_type = FCU_SLICE_P; fp.lambda = lambda; fp.search_range = search_range; fp.fast_search = fast_search;
   fill_params(e->c.p, width, height, fp);
-  const int m = FCU_REF_MARGIN, sy = width + 2 * m, sc = width / 2 + m;
-  e->c.ref_stride[0] = sy; e->c.ref_stride[1] = e->c.ref_stride[2] = sc;
-  e->c.ref[0] = py + (size_t)m * sy + m; e->c.ref[1] = pu + (size_t)(m / 2) * sc + m / 2; e->c.ref[2] = pv + (size_t)(m / 2) * sc + m / 2;
-  for (int k = 0; k < 3; k++) e->c.refs[0][k] = e->c.ref[k];
-  e->c.n_ref = 1; e->c.poc = 1; e->c.ref_poc[0] = 0; e->c.col_poc = 0; e->c.col_ref_poc[0] = -1;
+  const uint8_t *const planes[3] = { py, pu, pv };
+  const int ref_poc = 0;
+  chain_set_list0(e->c, 1, planes, &ref_poc, 1);            /* fcu_chain_set_reference */
 }
 /* several reference pictures: planes[3r .. 3r+2] = padded Y, U, V of RefPicList0[r] (after fcu_emu_set_p with planes[0..2]) */
 void fcu_emu_set_refs(void *h, int n, const uint8_t *const *planes, const int *pocs, int poc, const int *col_ref_pocs, int n_col)
 {
   EmuChain *e = (EmuChain *)h;
-  const int m = FCU_REF_MARGIN, sy = e->c.p.width + 2 * m, sc = e->c.p.width / 2 + m;
-  for (int r = 0; r < n; r++) {
-    e->c.refs[r][0] = planes[3 * r] + (size_t)m * sy + m; e->c.refs[r][1] = planes[3 * r + 1] + (size_t)(m / 2) * sc + m / 2; e->c.refs[r][2] = planes[3 * r + 2] + (size_t)(m / 2) * sc + m / 2;
-    e->c.ref_poc[r] = pocs[r];
-  }
-  e->c.n_ref = n; e->c.poc = poc; e->c.col_poc = pocs[0];
-  for (int k = 0; k < FCU_MAX_REF; k++) e->c.col_ref_poc[k] = k < n_col ? col_ref_pocs[k] : pocs[0] - 1;
+  chain_set_list0(e->c, n, planes, pocs, poc);              /* fcu_chain_set_references, then fcu_chain_set_collocated_pocs */
+  if (n_col > 0) chain_set_collocated_pocs(e->c, pocs[0], col_ref_pocs, n_col);
 }
 /* lambda of an I picture that is not the intra_main default (lowdelay_P: 0.57 * 0.85) */
 void fcu_emu_set_lambda(void *h, int qp, double lambda)
@@ -71,10 +59,7 @@ void fcu_emu_compress_ctu(void *h, int a) { EmuChain *e = (EmuChain *)h; compres
 void fcu_emu_get_state(void *h, uint8_t *ctx, uint64_t *frac) { EmuChain *e = (EmuChain *)h; memcpy(ctx, e->c.state.ctx, NCTX_INTRA); *frac = e->c.state.frac; }
 void fcu_emu_set_decision(void *h, int state, const uint8_t *sw_skip, const uint8_t *sw_term, int depth_exception, const int16_t *obf)
 {
-  Chain &c = ((EmuChain *)h)->c;
-  c.dec_state = state; c.depth_exception = depth_exception; c.obf = obf; c.obf_stride = c.p.width / 4;
-  for (int d = 0; d < 4; d++) { c.sw_skip[d] = sw_skip[d]; c.sw_term[d] = sw_term[d]; }
-  memset(c.ver, 0, sizeof(c.ver));
+  chain_set_decision(((EmuChain *)h)->c, state, depth_exception, obf, sw_skip, sw_term);
 }
 void fcu_emu_set_col(void *h, const fcu_ctu_out *col) { ((EmuChain *)h)->c.col = col; ((EmuChain *)h)->c.p.tmvp = col != nullptr; }
 void fcu_emu_set_amp(void *h, int amp) { ((EmuChain *)h)->c.p.amp = amp != 0; }

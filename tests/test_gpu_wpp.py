@@ -8,33 +8,9 @@ import pytest
 
 import hmo_py
 from wpp_oracle import wpp_oracle
+from wpp_testlib import _compare, _poisoned
 
 pytestmark = pytest.mark.gpu
-
-CTU_DT = np.dtype(hmo_py.Ctu)
-
-
-def _poisoned(eng, planes):
-    torch = eng.torch
-    dev = torch.device("cuda", eng.device)
-    rec = [torch.full(tuple(p.shape), 0x5A, dtype=torch.uint8, device=dev) for p in planes]
-    out = torch.full((eng.n_ctu * C.sizeof(hmo_py.Ctu),), 0xA5, dtype=torch.uint8, device=dev)
-    return rec, out
-
-
-def _compare(o, rec, out, what, eng=None, first=None):
-    got = np.frombuffer(out.cpu().numpy().tobytes(), CTU_DT)
-    want = np.frombuffer(o.enc.all_ctus_bytes(), CTU_DT)
-    for name in CTU_DT.names:
-        bad = np.nonzero([not np.array_equal(a, b) for a, b in zip(got[name], want[name])])[0]
-        assert bad.size == 0, f"{what}: field {name} differs at CTU {bad[:8].tolist()}"
-    for p, q in zip(rec, o.enc.rec):
-        assert np.array_equal(p.cpu().numpy(), q), what
-    if eng is not None:
-        for r in range(o.H):
-            ctx, frac = eng.ctx_state(first + r, full=True)
-            assert np.array_equal(ctx, o.row_state[r][0]) and frac == o.row_state[r][1], f"{what}: row {r} coder state"
-            assert eng.position(first + r) == (r + 1) * o.W
 
 
 def _run(pkg, Y, U, V, qp, **flags):

@@ -1,6 +1,6 @@
 """WaveFrontSynchro for P pictures on the MI355X: LowDelayPDecider(wpp=True) -- the rows of every clip's picture in one
 fcu_compress_wpp launch, the TZ search state handed from row to row and from picture to picture -- against the test-side
-P-slice WPP reference (tests/wpp_oracle_p.py) with the oracle's loop filters: every fcu_ctu_out field, the reconstruction
+P-slice WPP reference (tests/wpp_oracle.py) with the oracle's loop filters: every fcu_ctu_out field, the reconstruction
 before and after the loop filters, each row's coder state and the search state after every picture; plus the argument and
 state checks of fcu_wpp_begin_p / fcu_compress_wpp."""
 import ctypes as C
@@ -11,18 +11,10 @@ import pytest
 import hmo_py
 import search_trace as st
 from test_wpp_p_oracle import split_motion_clip
-from wpp_oracle_p import WppPOracle, wpp_p_clip
+from wpp_oracle import WppOracle, wpp_p_clip
+from wpp_testlib import CTU_DT, _compare_ctus
 
 pytestmark = pytest.mark.gpu
-
-CTU_DT = np.dtype(hmo_py.Ctu)
-
-
-def _compare_ctus(got_bytes, want_bytes, what):
-    got, want = np.frombuffer(got_bytes, CTU_DT), np.frombuffer(want_bytes, CTU_DT)
-    for name in CTU_DT.names:
-        bad = np.nonzero([not np.array_equal(a, b) for a, b in zip(got[name], want[name])])[0]
-        assert bad.size == 0, f"{what}: field {name} differs at CTU {bad[:8].tolist()}"
 
 
 def _check_picture(dec, r, R, what, rows=True):
@@ -144,8 +136,8 @@ def test_testing_state_set_before_the_search_state(pkg):
     obf_o, _ = hmo_py.obf_prepass(f1[0])
     sw = ((1, 1, 1, 1), (1, 1, 1, 1))
     _, qp, lam = hmo_py.ldp_slice(1, base_qp)
-    o = WppPOracle(*f1, qp, int_mv=state_in, decision=(hmo_py.TESTING, obf_o, sw[0], sw[1], 1), ref=want[0]["rec"], lambda_override=lam,
-                   search_range=sr, fast_search=1).run()
+    o = WppOracle(*f1, qp, int_mv=state_in, decision=(hmo_py.TESTING, obf_o, sw[0], sw[1], 1), ref=want[0]["rec"], lambda_override=lam,
+                  search_range=sr, fast_search=1).run()
     rows = (h + 63) // 64
     eng = pkg.CuEngine(w, h, max_chains=rows)
     fp = eng_mod.ldp_slice(base_qp, 1)

@@ -1,6 +1,6 @@
 """WaveFrontSynchro on pictures cut into slices of whole CTU rows, on the MI355X: fcu_wpp_begin_slices / fcu_compress_wpp -- the
 first row of every slice waits for nothing, the other rows for the row above in their slice -- against the test-side reference
-(tests/wpp_slices_oracle.py): every fcu_ctu_out field, the reconstruction, the rows' coder states, for P pictures the search
+(tests/wpp_oracle.py): every fcu_ctu_out field, the reconstruction, the rows' coder states, for P pictures the search
 state after every row; SequenceDecider and LowDelayPDecider end to end with the loop filters; and the argument and state checks
 of the entry point and of the launch.  Every GPU step is one bounded launch; nothing provokes the give-up path."""
 import ctypes as C
@@ -10,40 +10,10 @@ import pytest
 
 import hmo_py
 import search_trace as st
-from wpp_oracle import wpp_oracle
-from wpp_slices_oracle import WppSlicesOracle, wpp_slices_oracle, wpp_slices_p_clip
+from wpp_oracle import WppOracle, wpp_oracle, wpp_p_clip
+from wpp_testlib import CTU_DT, _compare, _compare_ctus, _poisoned
 
 pytestmark = pytest.mark.gpu
-
-CTU_DT = np.dtype(hmo_py.Ctu)
-
-
-def _poisoned(eng, planes):
-    torch = eng.torch
-    dev = torch.device("cuda", eng.device)
-    rec = [torch.full(tuple(p.shape), 0x5A, dtype=torch.uint8, device=dev) for p in planes]
-    out = torch.full((eng.n_ctu * C.sizeof(hmo_py.Ctu),), 0xA5, dtype=torch.uint8, device=dev)
-    return rec, out
-
-
-def _compare_ctus(got_bytes, want_bytes, what, n=None):
-    got, want = np.frombuffer(got_bytes, CTU_DT)[:n], np.frombuffer(want_bytes, CTU_DT)[:n]
-    assert len(got) == len(want) and len(got) > 0
-    for name in CTU_DT.names:
-        bad = np.nonzero([not np.array_equal(a, b) for a, b in zip(got[name], want[name])])[0]
-        assert bad.size == 0, f"{what}: field {name} differs at CTU {bad[:8].tolist()}"
-
-
-def _compare(o, rec, out, what, eng=None, first=None, sorted_ctx=False):
-    _compare_ctus(out.cpu().numpy().tobytes(), o.enc.all_ctus_bytes(), what)
-    for p, q in zip(rec, o.enc.rec):
-        assert np.array_equal(p.cpu().numpy(), q), what
-    if eng is not None:
-        sel = st.O_SORTED if sorted_ctx else slice(None)
-        for r in range(o.H):
-            ctx, frac = eng.ctx_state(first + r, full=True)
-            assert np.array_equal(ctx[sel], o.row_state[r][0][sel]) and frac == o.row_state[r][1], f"{what}: row {r} coder state"
-            assert eng.position(first + r) == (r + 1) * o.W
 
 
 # gen, w, h, qp, slice_rows: a subset of tests/test_wpp_slices_emu.py's I cases
@@ -51,7 +21,7 @@ def _compare(o, rec, out, what, eng=None, first=None, sorted_ctx=False):
                                           ("smooth", 136, 200, 37, 3), ("textured", 64, 192, 37, 2)])
 def test_small_i_pictures_match_the_reference(pkg, gen, w, h, qp, R):
     Y, U, V = getattr(pkg.synth, gen)(w, h, seed=9)
-    o = wpp_slices_oracle(Y, U, V, qp, R)
+    o = wpp_oracle(Y, U, V, qp, R)
     eng = pkg.CuEngine(w, h, max_chains=o.H)
     rec, out = _poisoned(eng, (Y, U, V))
     n, _, _ = eng.init_wpp_picture(0, (Y, U, V), qp, rec=rec, out=out, slice_rows=R)
@@ -84,7 +54,7 @@ def test_decision_states_match_the_reference(pkg):
     obf_dev = eng.obf_prepass(Y)[0][0].contiguous()
 
     def check(state, sw):
-        o = wpp_slices_oracle(Y, U, V, qp, R, decision=(state, obf_o, sw[0], sw[1], 0))
+        o = wpp_oracle(Y, U, V, qp, R, decision=(state, obf_o, sw[0], sw[1], 0))
         rec, out = _poisoned(eng, (Y, U, V))
         eng.init_wpp_picture(0, (Y, U, V), qp, rec=rec, out=out, slice_rows=R)
         for r in range(rows):
@@ -105,7 +75,7 @@ def test_several_sliced_pictures_in_one_launch_beyond_residency(pkg):
     row that waits always waits on a lower chain index, so ticket order still guarantees progress"""
     w, h, n_pics, seeds, R = 128, 1088, 256, 4, 2
     srcs = [pkg.synth.mixed(w, h, seed=s) for s in range(seeds)]
-    refs = [wpp_slices_oracle(*s, 32, R) for s in srcs]
+    refs = [wpp_oracle(*s, 32, R) for s in srcs]
     rows = (h + 63) // 64
     eng = pkg.CuEngine(w, h, max_chains=n_pics * rows)
     assert n_pics * rows > 256 * max(1, eng.lib.fcu_chains_per_cu())
@@ -130,7 +100,7 @@ def test_4k_rows_with_two_row_slices(pkg):
     n, _, _ = eng.init_wpp_picture(0, (Y, U, V), qp, rec=rec, out=out, slice_rows=R)
     assert n == 34
     eng.compress_wpp(0, n)
-    o = WppSlicesOracle(Y, U, V, qp, R).run(rows=rows)
+    o = WppOracle(Y, U, V, qp, R, rows=rows).run()
     nb = C.sizeof(hmo_py.Ctu)
     _compare_ctus(out.cpu().numpy().tobytes()[:rows * 60 * nb], o.enc.all_ctus_bytes()[:rows * 60 * nb], "4K R2")
     for p, q in zip([t.cpu().numpy() for t in rec], o.enc.rec):
@@ -150,7 +120,7 @@ def test_sequence_decider_with_sliced_wpp(pkg):
     assert "SliceArgument 8" in dec.slice_mode and "WaveFrontSynchro" in dec.slice_mode
     res = dec.decide_group(srcs)
     for (Y, U, V), r in zip(srcs, res):
-        o = wpp_slices_oracle(Y, U, V, qp, R)
+        o = wpp_oracle(Y, U, V, qp, R)
         o.enc.deblock()                                      # LFCrossSliceBoundaryFlag 1: across the slice boundaries
         _compare(o, r["rec"], r["out"], f"POC {r['poc']} deblocked")
     dec.close()
@@ -170,8 +140,8 @@ def test_lowdelay_clips_with_sliced_wpp_match_the_reference(pkg, case):
     """LowDelayPDecider(wpp=True, slice_rows=R): several pictures, deblocked (and SAO told the slice length where on)"""
     gen, w, h, base_qp, n_pic, sr, fast, (nref, rps), tmvp, amp, btab, R, sao = case
     frames = [st.moving_frame(pkg.synth, gen, w, h, 7, poc) for poc in range(n_pic)]
-    want = wpp_slices_p_clip(frames, base_qp, R, ref_pocs=lambda poc, n: pkg.lowdelay.ref_pocs(poc, n, rps), n_refs=nref, search_range=sr,
-                             fast_search=fast, tmvp=tmvp, amp=amp, cabac_b_table=btab, sao=sao)
+    want = wpp_p_clip(frames, base_qp, R, ref_pocs=lambda poc, n: pkg.lowdelay.ref_pocs(poc, n, rps), n_refs=nref, search_range=sr,
+                      fast_search=fast, tmvp=tmvp, amp=amp, cabac_b_table=btab, sao=sao)
     dec = pkg.lowdelay.LowDelayPDecider(w, h, base_qp, n_clips=1, search_range=sr, fast_search=fast, tmvp=bool(tmvp), amp=bool(amp),
                                         n_refs=nref, rps=rps, sao=sao, wpp=True, slice_rows=R)
     n_inter = 0
@@ -238,8 +208,8 @@ def test_argument_and_state_checks(pkg):
     assert lib.fcu_compress_wpp(eng.h, 3, 4, None) == -4     # a plain chain in the range
     assert lib.fcu_compress_wpp(eng.h, 0, 6, None) == 0      # both pictures
     assert lib.fcu_compress_wpp(eng.h, 0, 3, None) == -4     # already decided
-    _compare_ctus(out.cpu().numpy().tobytes(), wpp_slices_oracle(Y, U, V, 32, 2).enc.all_ctus_bytes(), "R2 of two pictures")
-    _compare_ctus(out2.cpu().numpy().tobytes(), wpp_slices_oracle(Y, U, V, 32, 1).enc.all_ctus_bytes(), "R1 of two pictures")
+    _compare_ctus(out.cpu().numpy().tobytes(), wpp_oracle(Y, U, V, 32, 2).enc.all_ctus_bytes(), "R2 of two pictures")
+    _compare_ctus(out2.cpu().numpy().tobytes(), wpp_oracle(Y, U, V, 32, 1).enc.all_ctus_bytes(), "R1 of two pictures")
 
     # a P row without a reference picture
     fpp = eng_mod.ldp_slice(32, 1)

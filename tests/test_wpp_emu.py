@@ -1,40 +1,11 @@
 """The engine source's WaveFrontSynchro row chains on the CPU wave emulator (tests/emu/wpp_emu.cpp) against the WPP
 reference (tests/wpp_oracle.py): every fcu_ctu_out field, the reconstruction and each row's final coder state."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import hmo_py
 from wpp_oracle import wpp_oracle
-
-EMU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="session")
-def wpp_emu(built):
-    """tests/emu/libwpp_emu.so, built with the g++ flags build() gives the other emulators"""
-    so, src = os.path.join(EMU, "libwpp_emu.so"), os.path.join(EMU, "wpp_emu.cpp")
-    csrc = os.path.join(ROOT, "fast-cu-decision-hevc_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")] + [os.path.join(ROOT, "include", "fcu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-shared", "-o", "libwpp_emu.so", "wpp_emu.cpp"], cwd=EMU)
-    lib = C.CDLL(so)
-    lib.wpp_emu_create.restype = C.c_void_p
-    lib.wpp_emu_create.argtypes = [C.c_int] * 4 + [C.c_void_p] * 7
-    lib.wpp_emu_destroy.argtypes = [C.c_void_p]
-    lib.wpp_emu_rows.argtypes = [C.c_void_p]
-    lib.wpp_emu_run.argtypes = [C.c_void_p]
-    lib.wpp_emu_set_decision.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.wpp_emu_get_state_full.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.wpp_emu_get_verify.argtypes = [C.c_void_p, C.c_void_p]
-    return lib
-
-
-TOOLS = 0b1011        # transform skip + its fast variant, no sign hiding, strong intra smoothing
+from wpp_testlib import TOOLS, assert_ctus_equal, emulate, flags_of, wpp_emu  # noqa: F401 (wpp_emu: the fixture)
 
 CASES = [
     ("mixed", 256, 192, 22, -1, None),
@@ -50,47 +21,19 @@ CASES = [
 @pytest.mark.parametrize("gen,w,h,qp,tools,state", CASES)
 def test_emulated_wpp_rows_are_bit_exact(wpp_emu, pkg, gen, w, h, qp, tools, state):
     Y, U, V = getattr(pkg.synth, gen)(w, h, seed=9)
-    flags = {}
-    if tools >= 0:
-        flags = dict(transform_skip=tools & 1, transform_skip_fast=(tools >> 1) & 1, sign_hiding=(tools >> 2) & 1, strong_smoothing=(tools >> 3) & 1)
     decision = None
     if state is not None:
         obf, _ = hmo_py.obf_prepass(Y)
         st = hmo_py.TESTING if state == "testing" else hmo_py.VERIFYING
         decision = (st, obf, (1, 1, 0, 1), (1, 0, 1, 1), 0)
-    o = wpp_oracle(Y, U, V, qp, decision=decision, **flags)
-
-    org = [np.ascontiguousarray(a) for a in (Y, U, V)]
-    rec = [np.full_like(a, 0x5A) for a in org]                # poisoned
-    n_ctu = o.W * o.H
-    out = (hmo_py.Ctu * n_ctu)()
-    C.memset(out, 0xA5, C.sizeof(out))
-    h_ = wpp_emu.wpp_emu_create(w, h, qp, tools, *[a.ctypes.data for a in org], *[a.ctypes.data for a in rec], C.addressof(out))
-    try:
-        assert wpp_emu.wpp_emu_rows(h_) == o.H
-        if decision is not None:
-            obf16 = np.ascontiguousarray(decision[1], np.int16)
-            sk, te = np.array(decision[2], np.uint8), np.array(decision[3], np.uint8)
-            wpp_emu.wpp_emu_set_decision(h_, decision[0], sk.ctypes.data, te.ctypes.data, decision[4], obf16.ctypes.data)
-        assert wpp_emu.wpp_emu_run(h_) == o.H
-        for a in range(n_ctu):
-            A = o.enc.ctu_arrays(a)
-            c = out[a]
-            for k, v in A.items():
-                g = getattr(c, k)
-                g = np.ctypeslib.as_array(g) if hasattr(g, "_length_") else g
-                assert np.array_equal(v, g) if isinstance(v, np.ndarray) else v == g, (a, k)
-        for p, q in zip(o.enc.rec, rec):
-            assert np.array_equal(p, q)
-        for r in range(o.H):
-            ctx = np.zeros(176, np.uint8)
-            frac = C.c_uint64(0)
-            wpp_emu.wpp_emu_get_state_full(h_, r, ctx.ctypes.data, C.byref(frac))
-            assert np.array_equal(ctx, o.row_state[r][0]) and frac.value == o.row_state[r][1], r
-        if state == "verifying":
-            v = np.zeros((4, 6), np.float64)
-            wpp_emu.wpp_emu_get_verify(h_, v.ctypes.data)
-            assert np.array_equal(v, o.verify)
-            assert v[:, :4].sum() > 0
-    finally:
-        wpp_emu.wpp_emu_destroy(h_)
+    o = wpp_oracle(Y, U, V, qp, decision=decision, **flags_of(tools))
+    e = emulate(wpp_emu, (Y, U, V), qp, tools=tools, decision=decision)       # (checks the row count, runs every row to its end)
+    assert len(e["states"]) == o.H
+    assert_ctus_equal(o.enc, e["out"])
+    for p, q in zip(o.enc.rec, e["rec"]):
+        assert np.array_equal(p, q)
+    for r in range(o.H):
+        assert np.array_equal(e["states"][r][0], o.row_state[r][0]) and e["states"][r][1] == o.row_state[r][1], r
+    if state == "verifying":
+        assert np.array_equal(e["verify"], o.verify)
+        assert e["verify"][:, :4].sum() > 0

@@ -1,11 +1,11 @@
-"""Properties of the test-side P-slice WaveFrontSynchro reference (tests/wpp_oracle_p.py) on the unchanged oracle: row 0 is the
+"""Properties of the test-side P-slice WaveFrontSynchro reference (tests/wpp_oracle.py) on the unchanged oracle: row 0 is the
 plain one-slice run, and its fixtures are sensitive to the TZ search state (m_integerMv2Nx2N) a partial bottom row takes from
 the row above and a picture takes from the picture before."""
 import numpy as np
 import pytest
 
 import hmo_py
-from wpp_oracle_p import WppPOracle, wpp_p_clip
+from wpp_oracle import WppOracle, wpp_p_clip
 
 
 def split_motion_clip(w, h, n_pic, seed, v=(14, 8), still=None):
@@ -47,7 +47,7 @@ def test_row_zero_is_the_plain_one_slice_run(built, pkg, gen, w, h, base_qp, fas
     _, qp, lam = hmo_py.ldp_slice(1, base_qp)
     state = [(3, -1), (0, 0), (0, 0), (0, 0)]
     kw = dict(ref=prev, lambda_override=lam, search_range=16, fast_search=fast)
-    o = WppPOracle(*f1, qp, int_mv=state, **kw).run()
+    o = WppOracle(*f1, qp, int_mv=state, **kw).run()
     ref = hmo_py.Encoder(*f1, qp, **kw)
     ref.set_int_mv(state)
     for a in range(o.W):
