@@ -297,6 +297,13 @@ struct Chain {
   int wpp, wpp_above;
   const uint8_t *wpp_sync_in;
   uint8_t *wpp_sync_out;
+  /* Tile of a one-slice picture (fcu_tiles_begin / fcu_wpp_begin_tiles), written by the host only: the CTU rectangle
+   * [tile_x0, tile_x0 + tile_w) x [tile_y0, tile_y0 + tile_h) the chain decides raster-in-tile.  next_ctu / end_ctu of the chain
+   * then count CTUs INSIDE the tile (position k = CTU (tile_x0 + k % tile_w, tile_y0 + k / tile_w)); a CTU outside the rectangle
+   * is no neighbour (TComDataCU::getPULeft ... CUIsFromSameSliceAndTile).  chain_bind sets the whole picture: position and
+   * picture address are then the same number and nothing is masked.  The fields sit in the tail fcu_chain_set_decision copies
+   * from the host descriptor, which therefore holds them too (ADVICE.md finding 4). */
+  int tile_x0, tile_y0, tile_w, tile_h;
 #ifdef FCU_EMU
   /* emulator only (the GPU layout has neither): bit r of wpp_mv_known = int_mv_r[r] holds HM's value (written by this row's
    * search, or taken from the caller / the row above); wpp_mv_rbw counts TZ searches that read a slot before it was known */
@@ -361,7 +368,10 @@ struct alignas(16) Scratch {
   alignas(16) int16_t memo_coef[MEMO_K * MEMO_POOL], memo_resi[MEMO_K * MEMO_POOL];
 };
 
-struct Env { Chain *C; Scratch *G; int cur_ctu, slice_start; };
+/* tx0 .. ty1: the chain's tile in CTUs, [tx0, tx1) x [ty0, ty1) (pictures are at most a few hundred CTUs wide) */
+struct Env { Chain *C; Scratch *G; int cur_ctu, slice_start; int16_t tx0, ty0, tx1, ty1; };
+/* CTU (cx, cy) lies in the tile of the chain (CUIsFromSameTile of a CTU of the picture) */
+FCU_DEV int in_tile(const Env E, int cx, int cy) { return cx >= E.tx0 && cx < E.tx1 && cy >= E.ty0 && cy < E.ty1; }
 /* transform unit descriptor (TComTU / TComTURecurse, TLibCommon/TComTU.cpp:47-207) */
 struct TU { int log2, tr_depth, part, nparts, x, y, off_y, cw, cwo, cx, cy, c_tr_depth, c_code_all, off_c, cu_depth, plast; };
 
@@ -1565,7 +1575,7 @@ FCU_DEV int unit_available(const Env E, int lx, int ly, int cx, int cy)
   const Params &P = E.C->p;
   if (lx < 0 || ly < 0 || lx >= P.width || ly >= P.height) return 0;
   const int ctuN = (ly >> 6) * E.C->w_ctu + (lx >> 6), ctuC = (cy >> 6) * E.C->w_ctu + (cx >> 6);
-  if (ctuN < E.slice_start) return 0;
+  if (ctuN < E.slice_start || !in_tile(E, lx >> 6, ly >> 6)) return 0;
   if (ctuN < ctuC) return 1;
   if (ctuN > ctuC) return 0;
   return zidx_of(lx, ly) < zidx_of(cx, cy);
@@ -1732,8 +1742,8 @@ FCU_DEV int nb_luma_dir(const Env E, const CuObj *cu, int lx, int ly)
   const fcu_ctu_out *c = &E.C->out[(ly >> 6) * E.C->w_ctu + (lx >> 6)]; const int p = zidx_of(lx, ly);
   return c->pred_mode[p] == MODE_INTRA ? c->intra_dir[0][p] : DC;
 }
-FCU_DEV int left_ctu_ok(const Env E, int lx, int ly) { if (lx == 0) return 0; if (lx & 63) return 1; return (ly >> 6) * E.C->w_ctu + (lx >> 6) - 1 >= E.slice_start; }
-FCU_DEV int above_ctu_ok(const Env E, int lx, int ly) { if (ly == 0) return 0; if (ly & 63) return 1; return (ly >> 6) * E.C->w_ctu + (lx >> 6) - E.C->w_ctu >= E.slice_start; }
+FCU_DEV int left_ctu_ok(const Env E, int lx, int ly) { if (lx == 0) return 0; if (lx & 63) return 1; return (ly >> 6) * E.C->w_ctu + (lx >> 6) - 1 >= E.slice_start && (lx >> 6) > E.tx0; }
+FCU_DEV int above_ctu_ok(const Env E, int lx, int ly) { if (ly == 0) return 0; if (ly & 63) return 1; return (ly >> 6) * E.C->w_ctu + (lx >> 6) - E.C->w_ctu >= E.slice_start && (ly >> 6) > E.ty0; }
 /* getIntraDirPredictor, TComDataCU.cpp:1542-1624 */
 FCU_DEV int intra_dir_predictor(const Env E, const CuObj *cu, int part, int *preds)
 {
@@ -3605,24 +3615,35 @@ FCU_DEV void load_hot_tables()
  * the second CTU of its own row it saves its contexts for the row below (:1514-1517).  A row that starts a slice (slices of whole
  * rows, fcu_wpp_begin_slices) is the first CTU of its slice: the slice's reset alone, row_start false, wpp_sync_in never read
  * (CUIsFromSameSliceAndTile(pCtuTR) fails at :1400, nothing is loaded); its above neighbours are masked by E.slice_start.  Every
- * row saves after its second CTU, whether or not a row of its slice follows.  WPP = false is the plain chain. */
+ * row saves after its second CTU, whether or not a row of its slice follows.  WPP = false is the plain chain.
+ * Tiles (fcu_tiles_begin / fcu_wpp_begin_tiles; one slice per picture): `pos` counts CTUs inside the chain's tile, raster-in-tile,
+ * and the CTU's picture address follows from it; without tiles the tile is the picture and both are the same number.  The first
+ * CTU of a tile resets the coder as the first CTU of a slice does (:1392-1395); "first column" and "second column" of the
+ * WaveFrontSynchro rules are those of the tile (tileXPosInCtus, :1396 and :1514), and a one-CTU-wide tile loads nothing (its
+ * above-right CTU is in another tile: CUIsFromSameSliceAndTile fails).  end_of_slice_segment_flag is 1 at the picture's last CTU
+ * in tile-scan order only -- the last CTU of the last tile, which is the CTU at the picture's last address; the last CTU of any
+ * other tile codes a 0 there (its substream ends with it, :1718-1727, which touches no context). */
 template <bool WPP = false>
-FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int ctuRsAddr)
+FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int pos)
 {
-  C = FCU_UNI(C); G = FCU_UNI(G); ctuRsAddr = FCU_UNI(ctuRsAddr);
+  C = FCU_UNI(C); G = FCU_UNI(G); pos = FCU_UNI(pos);
   Env E; E.C = C; E.G = G;
   FCU_TIC(t10_);
   const Params &P = C->p;
+  const int tileW = FCU_UNI(C->tile_w), tileX0 = FCU_UNI(C->tile_x0), tileY0 = FCU_UNI(C->tile_y0);
+  const int col = pos % tileW;                                /* column inside the tile */
+  const int ctuRsAddr = FCU_UNI((tileY0 + pos / tileW) * C->w_ctu + tileX0 + col);
+  E.tx0 = (int16_t)tileX0; E.ty0 = (int16_t)tileY0; E.tx1 = (int16_t)(tileX0 + tileW); E.ty1 = (int16_t)(tileY0 + FCU_UNI(C->tile_h));
   const int sliceLen = P.slice_ctus > 0 ? P.slice_ctus : C->n_ctu;
   const int sliceStart = (ctuRsAddr / sliceLen) * sliceLen;
   int sliceEnd = sliceStart + sliceLen; if (sliceEnd > C->n_ctu) sliceEnd = C->n_ctu;
   E.cur_ctu = ctuRsAddr; E.slice_start = sliceStart;
   fcu_ctu_out *out = &C->out[ctuRsAddr];
   const int x = (ctuRsAddr % C->w_ctu) * CTU, y = (ctuRsAddr / C->w_ctu) * CTU;
-  const int col = ctuRsAddr % C->w_ctu;
-  const bool row_start = WPP && col == 0 && ctuRsAddr != sliceStart;
-  FCU_SERIAL { g_S.env = E; g_S.ref_tag = -1; if (ctuRsAddr == sliceStart || row_start) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
-  if (row_start && C->w_ctu >= 2) {
+  const bool unit_start = ctuRsAddr == sliceStart || pos == 0;      /* first CTU of a slice or of a tile */
+  const bool row_start = WPP && col == 0 && !unit_start;
+  FCU_SERIAL { g_S.env = E; g_S.ref_tag = -1; if (unit_start || row_start) cab_init(slot_ptr(E, 0, CI_CURR_BEST), P.qp, P.slice_type, P.cabac_b_table); else cab_copy1(slot_ptr(E, 0, CI_CURR_BEST), &C->state); }
+  if (row_start && tileW >= 2) {
     const uint8_t *src = C->wpp_sync_in;
     FCU_FOR_LANES { Cabac *d = slot_ptr(E, 0, CI_CURR_BEST); for (int i = lane; i < NCTX; i += 64) d->ctx[i] = src[i]; }   /* lane-indexed: vector loads */
   }
@@ -3733,7 +3754,9 @@ FCU_DEV void wpp_publish(unsigned *ctl_, int chain, unsigned done)
  * precedes its last publish.  Lane-indexed loads (vector memory, never the scalar cache: Guideline 16 Pitfall 6).
  * Slices of whole rows: "the first row" reads "the first row of the slice" throughout.  A row that starts a slice takes nothing
  * from the chain before it, at its start or at its end: it begins from its own descriptor (zero after binding: the convention
- * for slices decided side by side), so the last row chain of a slice ends with the state after that slice. */
+ * for slices decided side by side), so the last row chain of a slice ends with the state after that slice.
+ * Tiles: the same with "tile" for "slice" -- the first row of every tile starts from its own descriptor (zero after binding; HM's
+ * tile-scan walk would carry the state from the tile before), and the last row chain of a tile ends with the state after it. */
 FCU_DEV void wpp_take_search_state(Chain *C, const Chain *A, int first, int end)
 {
   FCU_FOR_LANES {
@@ -3751,12 +3774,14 @@ FCU_DEV FCU_NOINLINE int run_wpp_chain(Chain *C, Scratch *G, unsigned *ctl, int 
 {
   C = FCU_UNI(C); G = FCU_UNI(G); ctl = FCU_UNI(ctl); chain = FCU_UNI(chain);
   load_hot_tables();
-  const int above = FCU_UNI(C->wpp_above), W = FCU_UNI(C->w_ctu), end = FCU_UNI(C->end_ctu);
+  /* W, and x below: the width of the chain's tile and the column inside it (the picture's without tiles); first / end count CTUs
+   * inside the tile.  A row waits for min(x + 2, W) CTUs of the row above IN ITS TILE and for nothing of another tile. */
+  const int above = FCU_UNI(C->wpp_above), W = FCU_UNI(C->tile_w), end = FCU_UNI(C->end_ctu);
   const int first = FCU_UNI(C->next_ctu);
   /* P row below the first of its slice: the row above's descriptor (rows of a picture are consecutive chains) and the hand-off rule above */
   const bool inherit = above >= 0 && C->p.slice_type == SLICE_P;
   const Chain *A = C + (above - chain);
-  const bool tz = C->p.fast_search != 0, full_first = C->p.width >= CTU && (first / W + 1) * CTU <= C->p.height;
+  const bool tz = C->p.fast_search != 0, full_first = (FCU_UNI(C->tile_x0) + 1) * CTU <= C->p.width && (FCU_UNI(C->tile_y0) + first / W + 1) * CTU <= C->p.height;
 #ifdef FCU_EMU
   if (above >= 0) C->wpp_mv_known = 0;                       /* (a row that starts a slice keeps what its binder declared known) */
 #endif

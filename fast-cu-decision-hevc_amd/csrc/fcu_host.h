@@ -3,7 +3,7 @@
  * slice with libm (lambda, sqrt(lambda), chroma distortion weight, RDOQ lambdas, RDOQ error
  * scales, sign-hiding rdFactor).  They are handed to the kernels as f64/i64 bit patterns so
  * that no transcendental is ever evaluated on the device.
- * Also the host-side fills of the chain descriptor (chain_bind ... wpp_bind_row), the one copy
+ * Also the host-side fills of the chain descriptor (chain_bind ... wpp_bind_row, tile_bind), the one copy
  * libfcu.so and the test-only emulators bind a chain with.
  */
 #pragma once
@@ -96,6 +96,7 @@ inline void chain_bind(Chain &h, int width, int height, const fcu_frame_params &
   h.out = out;
   h.w_ctu = (width + 63) / 64; h.h_ctu = (height + 63) / 64; h.n_ctu = h.w_ctu * h.h_ctu;
   h.next_ctu = 0; h.end_ctu = h.n_ctu;
+  h.tile_x0 = 0; h.tile_y0 = 0; h.tile_w = h.w_ctu; h.tile_h = h.h_ctu;     /* no tiles: the tile is the picture */
 }
 
 /* list 0 of a bound P chain: pad_planes[3r .. 3r+2] = first byte of the padded Y, U, V planes of RefPicList0[r] (luma border
@@ -157,5 +158,48 @@ inline void wpp_bind_row(Chain &h, int r, int W, int slice_rows, int first_chain
   h.wpp_sync_in = ra >= 0 ? sync + (size_t)WPP_SYNC_BYTES * (first_chain + ra) : nullptr;
   h.wpp_sync_out = sync + (size_t)WPP_SYNC_BYTES * (first_chain + r);
 }
+
+/* ---- Tiles of a one-slice picture (fcu_tiles_begin / fcu_wpp_begin_tiles): the rules of the binding, shared by libfcu.so and
+ * the test-only emulator driver.
+ * tile_grid: TComPicSym::initTiles with TileUniformSpacing -- column i spans the CTU columns [i * W / C, (i + 1) * W / C), rows
+ * likewise.  col_bd receives n_cols + 1 boundaries, row_bd n_rows + 1 (either may be null).  false = no grid: a count below 1,
+ * or more columns / rows than the picture has CTU columns / rows (a tile would be empty). */
+inline bool tile_grid(int W, int H, int n_cols, int n_rows, int *col_bd, int *row_bd)
+{
+  if (W < 1 || H < 1 || n_cols < 1 || n_rows < 1 || n_cols > W || n_rows > H) return false;
+  if (col_bd) for (int i = 0; i <= n_cols; i++) col_bd[i] = (int)((long long)i * W / n_cols);
+  if (row_bd) for (int i = 0; i <= n_rows; i++) row_bd[i] = (int)((long long)i * H / n_rows);
+  return true;
+}
+/* chains a picture of W x H CTUs needs as n_cols x n_rows tiles: one per tile, or with WaveFrontSynchro inside the tiles one per
+ * CTU row of every tile (= n_cols x H).  -1 = no such grid. */
+inline int tile_chains(int W, int H, int n_cols, int n_rows, int wpp)
+{
+  if (!tile_grid(W, H, n_cols, n_rows, nullptr, nullptr)) return -1;
+  return wpp ? n_cols * H : n_cols * n_rows;
+}
+/* what the tile binders refuse in the frame parameters: SliceMode 1 together with tiles, and TMVP across tile columns (HM's
+ * collocated bottom-right candidate reads across the tile edge) */
+inline bool tile_params_ok(const fcu_frame_params &fp, int n_cols) { return fp.slice_ctus == 0 && !(fp.tmvp && n_cols > 1); }
+/* the tile part of a descriptor chain_bind has filled: the rectangle, and the chain's range = the whole tile, counted inside it */
+inline void tile_bind(Chain &h, int x0, int y0, int w, int hh)
+{
+  h.tile_x0 = x0; h.tile_y0 = y0; h.tile_w = w; h.tile_h = hh;
+  h.next_ctu = 0; h.end_ctu = w * hh;
+}
+/* WaveFrontSynchro inside a tile: row r of the tile tile_bind gave the descriptor, as chain `chain`; the rows of a tile are
+ * consecutive chains top to bottom, so the row above is chain - 1.  Row 0 of a tile is bound as a row that starts a slice is:
+ * nothing above, no slot to read (wpp_bind_row). */
+inline void wpp_bind_tile_row(Chain &h, int r, int chain, uint8_t *sync)
+{
+  h.next_ctu = r * h.tile_w; h.end_ctu = (r + 1) * h.tile_w;
+  h.wpp = 1; h.wpp_above = r > 0 ? chain - 1 : -1;
+  h.wpp_sync_in = r > 0 ? sync + (size_t)WPP_SYNC_BYTES * (chain - 1) : nullptr;
+  h.wpp_sync_out = sync + (size_t)WPP_SYNC_BYTES * chain;
+}
+/* picture address of position `pos` of the chain's tile (what compress_ctu derives on the device) */
+inline int tile_ctu_addr(const Chain &h, int pos) { return (h.tile_y0 + pos / h.tile_w) * h.w_ctu + h.tile_x0 + pos % h.tile_w; }
+inline bool tile_is_picture(const Chain &h) { return h.tile_x0 == 0 && h.tile_y0 == 0 && h.tile_w == h.w_ctu && h.tile_h == h.h_ctu; }
+inline bool tile_is_last(const Chain &h) { return h.tile_x0 + h.tile_w == h.w_ctu && h.tile_y0 + h.tile_h == h.h_ctu; }
 
 } // namespace fcu

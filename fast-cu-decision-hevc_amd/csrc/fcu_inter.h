@@ -71,7 +71,7 @@ FCU_DEV Nb nb_motion(const Env E, const CuObj *cu, int nx, int ny, int cx, int c
   const Params &P = E.C->p;
   if (nx < 0 || ny < 0 || nx >= P.width || ny >= P.height) return r;
   const int ctuN = (ny >> 6) * E.C->w_ctu + (nx >> 6), ctuC = (cy >> 6) * E.C->w_ctu + (cx >> 6);
-  if (ctuN < E.slice_start || ctuN > ctuC) return r;
+  if (ctuN < E.slice_start || ctuN > ctuC || !in_tile(E, nx >> 6, ny >> 6)) return r;
   if (ctuN == ctuC && !(zidx_of(nx, ny) < zidx_of(cx, cy))) return r;
   r.avail = 1;
   if (inside_cu(cu, nx, ny)) {

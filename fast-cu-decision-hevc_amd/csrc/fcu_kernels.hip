@@ -289,6 +289,7 @@ int fcu_chain_set_range(fcu_ctx *c, int chain, int first_ctu, int n_ctus)
   Chain &h = c->h_chains[(size_t)chain];
   if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_range: chain not bound (fcu_chain_begin)");
   if (h.wpp) return fail(FCU_ERR_STATE, "fcu_chain_set_range: a WaveFrontSynchro row chain keeps the row fcu_wpp_begin gave it");
+  if (!tile_is_picture(h)) return fail(FCU_ERR_STATE, "fcu_chain_set_range: a tile chain keeps the tile fcu_tiles_begin gave it");
   const int sl = h.p.slice_ctus;
   if (first_ctu < 0 || n_ctus <= 0 || first_ctu + n_ctus > h.n_ctu) return fail(FCU_ERR_ARG, "fcu_chain_set_range: range outside the frame");
   /* a chain may only start where the reference resets its entropy coder and cuts the neighbourhood: at a slice start */
@@ -328,6 +329,20 @@ int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream
 
 int fcu_wpp_rows(const fcu_ctx *c) { return c ? (c->sp.height + 63) / 64 : 0; }
 
+/* the control words and sync slots of WaveFrontSynchro launches, allocated by the first binder that needs them */
+static int wpp_alloc(fcu_ctx *c, const char *name)
+{
+  if (c->d_wpp_ctl) return FCU_OK;
+  const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
+  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipMalloc((void **)&c->d_wpp_ctl, ctl));
+  if (hipMalloc((void **)&c->d_wpp_sync, (size_t)WPP_SYNC_BYTES * c->sp.max_chains) != hipSuccess) {
+    hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, std::string(name) + ": out of device memory");
+  }
+  c->wpp_ctl_bytes = ctl;
+  return FCU_OK;
+}
+
 /* the binding the WPP entry points share: `name` for the messages, the slice type already checked by the caller.  slice_rows
  * 0 = a one-slice picture (fp->slice_ctus must be 0); slice_rows R >= 1 (fcu_wpp_begin_slices) = slices of R whole CTU rows.
  * A row that starts a slice is bound as a row 0 is: no row above (wpp_above -1) and no sync slot to read, so run_wpp_chain
@@ -346,15 +361,7 @@ static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp_in, 
     fp_sliced.slice_ctus = sl; fp = &fp_sliced;
   }
   if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains for one chain per CTU row (fcu_wpp_rows)");
-  if (!c->d_wpp_ctl) {
-    const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
-    HIPCHK(hipSetDevice(c->sp.device));
-    HIPCHK(hipMalloc((void **)&c->d_wpp_ctl, ctl));
-    if (hipMalloc((void **)&c->d_wpp_sync, (size_t)WPP_SYNC_BYTES * c->sp.max_chains) != hipSuccess) {
-      hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, std::string(name) + ": out of device memory");
-    }
-    c->wpp_ctl_bytes = ctl;
-  }
+  { const int rc = wpp_alloc(c, name); if (rc != FCU_OK) return rc; }
   const int rc = fcu_chain_begin(c, first_chain, fp, oy, ou, ov, ry, ru, rv, dev_out);     /* checks the rest, fills the row-0 descriptor */
   if (rc != FCU_OK) return rc;
   const Chain base = c->h_chains[(size_t)first_chain];
@@ -392,6 +399,63 @@ int fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *fp
   return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_slices", slice_rows, oy, ou, ov, ry, ru, rv, dev_out);     /* the slice type: fcu_chain_begin's check */
 }
 
+/* ---- tiles of a one-slice picture */
+int fcu_tile_grid(int width_in_ctus, int height_in_ctus, int n_cols, int n_rows, int *col_bd, int *row_bd)
+{
+  if (!tile_grid(width_in_ctus, height_in_ctus, n_cols, n_rows, col_bd, row_bd)) return fail(FCU_ERR_ARG, "fcu_tile_grid: a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
+  return FCU_OK;
+}
+
+int fcu_tile_chains(const fcu_ctx *c, int n_cols, int n_rows, int wpp)
+{
+  return c ? tile_chains((c->sp.width + 63) / 64, (c->sp.height + 63) / 64, n_cols, n_rows, wpp) : -1;
+}
+
+/* the binding fcu_tiles_begin and fcu_wpp_begin_tiles share: chain_bind (through fcu_chain_begin, which checks the frame
+ * parameters) for the first chain, then every tile in tile-scan order through tile_bind, and with wpp every CTU row of the tile
+ * through wpp_bind_tile_row */
+static int tiles_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows, int wpp, const char *name,
+                      const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  if (!c || !fp) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
+  const int W = (c->sp.width + 63) / 64, H = (c->sp.height + 63) / 64;
+  std::vector<int> cb((size_t)(n_cols > 0 ? n_cols : 0) + 1), rb((size_t)(n_rows > 0 ? n_rows : 0) + 1);
+  if (!tile_grid(W, H, n_cols, n_rows, cb.data(), rb.data())) return fail(FCU_ERR_ARG, std::string(name) + ": a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
+  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": tiles need one slice per picture (slice_ctus 0)");
+  if (!tile_params_ok(*fp, n_cols)) return fail(FCU_ERR_ARG, std::string(name) + ": TMVP across tile columns is not supported (tmvp 1 needs n_cols 1)");
+  const int n = tile_chains(W, H, n_cols, n_rows, wpp);
+  if (first_chain < 0 || first_chain + n > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains (fcu_tile_chains)");
+  if (wpp) { const int rc = wpp_alloc(c, name); if (rc != FCU_OK) return rc; }
+  const int rc = fcu_chain_begin(c, first_chain, fp, oy, ou, ov, ry, ru, rv, dev_out);
+  if (rc != FCU_OK) return rc;
+  const Chain base = c->h_chains[(size_t)first_chain];
+  int i = first_chain;
+  for (int ty = 0; ty < n_rows; ty++) for (int tx = 0; tx < n_cols; tx++) {
+    const int x0 = cb[(size_t)tx], y0 = rb[(size_t)ty], tw = cb[(size_t)tx + 1] - x0, th = rb[(size_t)ty + 1] - y0;
+    for (int r = 0; r < (wpp ? th : 1); r++, i++) {
+      Chain &h = c->h_chains[(size_t)i];
+      h = base;
+      tile_bind(h, x0, y0, tw, th);
+      if (wpp) wpp_bind_tile_row(h, r, i, c->d_wpp_sync);
+      c->h_pos[(size_t)i] = h.next_ctu;
+    }
+  }
+  HIPCHK(hipMemcpy(&c->d_chains[first_chain], &c->h_chains[(size_t)first_chain], sizeof(Chain) * (size_t)n, hipMemcpyHostToDevice));
+  return FCU_OK;
+}
+
+int fcu_tiles_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
+                    const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  return tiles_bind(c, first_chain, fp, n_cols, n_rows, 0, "fcu_tiles_begin", oy, ou, ov, ry, ru, rv, dev_out);
+}
+
+int fcu_wpp_begin_tiles(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
+                        const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
+{
+  return tiles_bind(c, first_chain, fp, n_cols, n_rows, 1, "fcu_wpp_begin_tiles", oy, ou, ov, ry, ru, rv, dev_out);
+}
+
 /* the rows of a P picture decide one picture: every row must name row 0's reference pictures and collocated field */
 static bool wpp_same_refs(const Chain &a, const Chain &b)
 {
@@ -409,26 +473,37 @@ static bool wpp_same_refs(const Chain &a, const Chain &b)
 int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
 {
   if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
+  int pic0 = first;                                         /* first chain of the picture chain i belongs to */
   for (int i = first; i < first + n; i++) {
     const Chain &h = c->h_chains[(size_t)i];
-    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices");
+    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles");
     /* a picture starts with its row 0 (at `first` or right after the last row of the picture before it) and its rows follow at
      * consecutive chains; a row without a row above that is not row 0 must be the first row of a slice of whole rows of the
      * picture the chain before it belongs to (fcu_wpp_begin_slices) */
-    const int row = h.next_ctu / h.w_ctu, slice_rows = h.p.slice_ctus / h.w_ctu;      /* slice_ctus 0 = one slice: slice_rows 0, every row below row 0 has a row above */
+    /* with tiles (fcu_wpp_begin_tiles; slice_ctus 0) "row" is the row inside the chain's tile and positions count inside it: the
+     * tiles of a picture follow each other in tile-scan order, each with its rows at consecutive chains, and a picture ends with
+     * the last row of its last tile.  Without tiles the tile is the picture and the rules read as before. */
+    const int row = h.next_ctu / h.tile_w, slice_rows = h.p.slice_ctus / h.w_ctu;      /* slice_ctus 0 = one slice: slice_rows 0, every row below row 0 has a row above */
+    const Chain *b = i > first ? &c->h_chains[(size_t)i - 1] : nullptr;
+    const bool b_ends_tile = b && b->end_ctu == b->tile_w * b->tile_h;
     bool starts_ok;
-    if (row == 0) starts_ok = h.wpp_above < 0 && (i == first || c->h_chains[(size_t)i - 1].end_ctu == c->h_chains[(size_t)i - 1].n_ctu);
+    if (row == 0 && h.tile_x0 == 0 && h.tile_y0 == 0) { starts_ok = h.wpp_above < 0 && (i == first || (b_ends_tile && tile_is_last(*b))); pic0 = i; }
+    else if (row == 0) {                                    /* the tile after b's in tile-scan order: to its right, or the first of the next tile row */
+      const bool b_row_end = b && b->tile_x0 + b->tile_w == b->w_ctu;
+      starts_ok = h.wpp_above < 0 && b_ends_tile && b->out == h.out &&
+                  (b_row_end ? h.tile_x0 == 0 && h.tile_y0 == b->tile_y0 + b->tile_h : h.tile_x0 == b->tile_x0 + b->tile_w && h.tile_y0 == b->tile_y0);
+    }
     else {
       const int ra = wpp_row_above(row, slice_rows);
-      const Chain *b = i > first ? &c->h_chains[(size_t)i - 1] : nullptr;
-      starts_ok = b && b->out == h.out && b->end_ctu == h.next_ctu && b->p.slice_ctus == h.p.slice_ctus && h.wpp_above == (ra >= 0 ? i - 1 : -1);
+      starts_ok = b && b->out == h.out && b->end_ctu == h.next_ctu && b->p.slice_ctus == h.p.slice_ctus && h.wpp_above == (ra >= 0 ? i - 1 : -1)
+                  && b->tile_x0 == h.tile_x0 && b->tile_y0 == h.tile_y0 && b->tile_w == h.tile_w && b->tile_h == h.tile_h;
     }
-    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices, their rows at consecutive chains");
-    if (i == first + n - 1 && h.end_ctu != h.n_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture");
-    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin(_p) / fcu_wpp_begin_slices)");
+    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles, their rows at consecutive chains (tiles: in tile-scan order, the rows of a tile top to bottom)");
+    if (i == first + n - 1 && !(h.end_ctu == h.tile_w * h.tile_h && tile_is_last(h))) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture (tiles: of its last tile)");
+    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles)");
     if (h.p.slice_type == SLICE_P) {
       if (h.ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_wpp: P row without reference picture (fcu_chain_set_reference(s) on every row)");
-      const Chain &row0 = c->h_chains[(size_t)(i - (h.next_ctu / h.w_ctu))];
+      const Chain &row0 = c->h_chains[(size_t)pic0];
       if (!wpp_same_refs(h, row0)) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the rows of a P picture name different reference pictures or collocated fields");
     }
   }
@@ -480,7 +555,8 @@ int fcu_chain_position(fcu_ctx *c, int chain)
 int fcu_compress_ctu(fcu_ctx *c, int chain, uint32_t ctuRsAddr, fcu_ctu_out *host_out)
 {
   if (!c || chain < 0 || chain >= c->sp.max_chains || !host_out) return fail(FCU_ERR_ARG, "fcu_compress_ctu: bad argument");
-  if ((int)ctuRsAddr != c->h_pos[(size_t)chain] || (int)ctuRsAddr >= c->h_chains[(size_t)chain].end_ctu) return fail(FCU_ERR_STATE, "fcu_compress_ctu: CTUs of a chain must be decided in raster order");
+  /* (a tile chain's position counts CTUs inside its tile; the CTU is still named by its picture address) */
+  if (c->h_pos[(size_t)chain] >= c->h_chains[(size_t)chain].end_ctu || c->h_chains[(size_t)chain].out == nullptr || (int)ctuRsAddr != tile_ctu_addr(c->h_chains[(size_t)chain], c->h_pos[(size_t)chain])) return fail(FCU_ERR_STATE, "fcu_compress_ctu: CTUs of a chain must be decided in raster order");
   int r = fcu_compress_chains(c, chain, 1, 1, nullptr);
   if (r != FCU_OK) return r;
   HIPCHK(hipDeviceSynchronize());

@@ -87,7 +87,8 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_build_info", "fcu_abi_sizeof", "fcu_tcm_threshold", "fcu_chain_set_reference", "fcu_pad_reference", "fcu_pad_sizes", "fcu_ldp_slice", "fcu_get_ctx_state_full",
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
-           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices"]
+           "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
+           "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -170,6 +171,10 @@ def load_lib():
     lib.fcu_wpp_begin_p.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams)] + [C.c_void_p] * 7
     lib.fcu_wpp_begin_slices.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int] + [C.c_void_p] * 7
     lib.fcu_compress_wpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.fcu_tile_grid.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2
+    lib.fcu_tile_chains.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.fcu_tiles_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int, C.c_int] + [C.c_void_p] * 7
+    lib.fcu_wpp_begin_tiles.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int, C.c_int] + [C.c_void_p] * 7
     _lib = lib
     return lib
 
@@ -221,6 +226,15 @@ def ldp_slice(base_qp, poc):
     fp = FrameParams()
     load_lib().fcu_ldp_slice(C.byref(fp), base_qp, poc)
     return fp
+
+
+def tile_grid(width_in_ctus, height_in_ctus, n_cols, n_rows):
+    """fcu_tile_grid: HM's uniform tile spacing -> (column boundaries [n_cols + 1], row boundaries [n_rows + 1]) in CTUs.
+    Raises ValueError for a grid with an empty tile.  Host arithmetic of libfcu.so; needs no GPU."""
+    cb, rb = (C.c_int * (max(n_cols, 0) + 1))(), (C.c_int * (max(n_rows, 0) + 1))()
+    if load_lib().fcu_tile_grid(width_in_ctus, height_in_ctus, n_cols, n_rows, cb, rb) != 0:
+        raise ValueError(f"no {n_cols} x {n_rows} tile grid on a picture of {width_in_ctus} x {height_in_ctus} CTUs (a tile would be empty)")
+    return list(cb), list(rb)
 
 
 def frame_state(poc, period=60, n_training=2, n_verifying=1):
@@ -410,6 +424,48 @@ class CuEngine:
         if p_slice and search_state is not None:
             self.set_search_state(first_chain, search_state)
         return n_rows, rec, out
+
+    def tile_chains(self, n_cols, n_rows, wpp=False):
+        """chains init_tile_picture binds for this grid (fcu_tile_chains); -1: no such grid"""
+        return self.lib.fcu_tile_chains(self.h, n_cols, n_rows, int(bool(wpp)))
+
+    def init_tile_picture(self, first_chain, org, qp, n_cols, n_rows, wpp=False, rec=None, out=None, params=None, ref=None, refs=None,
+                          ref_pocs=None, poc=None, col_ref_pocs=None, col=None, **flags):
+        """One picture, one slice, cut into n_cols x n_rows uniform tiles (HM's TileUniformSpacing).  wpp=False: chains
+        [first_chain, first_chain + n_cols * n_rows) become its tiles in tile-scan order (fcu_tiles_begin) and compress_chains
+        advances them, each raster-in-tile.  wpp=True: WaveFrontSynchro inside every tile -- one chain per CTU row of every tile,
+        tiles in tile-scan order, rows top to bottom (fcu_wpp_begin_tiles), decided by compress_wpp.  The chains share the
+        picture's planes and fcu_ctu_out array.  params / flags: the frame parameters as init_chain takes them (I or P by
+        params.slice_type); a P picture takes ref or refs / ref_pocs / poc / col_ref_pocs and col on every chain.  Every tile
+        starts from a zero search state.  Returns (n_chains, rec, out)."""
+        if refs is not None:
+            assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
+        if rec is None:
+            rec = [torch.zeros_like(p) for p in planes]
+        if out is None:
+            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
+        fp = FrameParams()
+        if params is not None:
+            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
+        else:
+            self.lib.fcu_default_frame_params(C.byref(fp), qp)
+        known = {n for n, _ in FrameParams._fields_}
+        for k, v in flags.items():
+            if k not in known:
+                raise TypeError(f"init_tile_picture: unknown frame parameter {k!r}")
+            setattr(fp, k, v)
+        ptrs = [p.data_ptr() for p in planes] + [p.data_ptr() for p in rec] + [out.data_ptr()]
+        begin, name = (self.lib.fcu_wpp_begin_tiles, "fcu_wpp_begin_tiles") if wpp else (self.lib.fcu_tiles_begin, "fcu_tiles_begin")
+        self._chk(begin(self.h, first_chain, C.byref(fp), int(n_cols), int(n_rows), *ptrs), name)
+        n = self.tile_chains(n_cols, n_rows, wpp)
+        for k in range(n):
+            self._keep[first_chain + k] = (planes, rec, out)
+            if fp.slice_type == SLICE_P:
+                self._bind_refs(first_chain + k, ref, refs, ref_pocs, poc, col_ref_pocs, col)
+        return n, rec, out
 
     def compress_wpp(self, first, n, stream=None):
         """decides the WPP row chains [first, first + n) (whole pictures) to the end in one launch; returns once it has finished"""

@@ -56,9 +56,22 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
-        rps: which pictures those are (ref_pocs above)."""
+        rps: which pictures those are (ref_pocs above).
+        tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
+        (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles: one chain per CTU row of every
+        tile).  Every tile of every picture starts from a zero search state.  Not with slice_ctus / slice_rows, not with sao, and
+        not with tmvp when C > 1."""
+        if tiles is not None:
+            if slice_ctus or slice_rows is not None:
+                raise ValueError("LowDelayPDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
+            if sao:
+                raise ValueError("LowDelayPDecider: sao=True together with tiles is not supported (SAO merge candidates must not cross tiles; fcu_sao is not taught that)")
+            _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
+            if tmvp and tiles[0] > 1:
+                raise ValueError("LowDelayPDecider: tmvp together with tile columns is not supported (the collocated bottom-right candidate reads across the tile edge)")
+        self.tiles = tiles
         if wpp and slice_ctus:
             raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
         if slice_rows is not None and not wpp:
@@ -74,6 +87,8 @@ class LowDelayPDecider:
         if slice_rows is not None:
             self.sao_slice_ctus = slice_rows * ((width + 63) // 64)
         self.n_chains = (height + 63) // 64 if wpp else self.n_slices          # chains per picture: rows (WPP) or slices
+        if tiles is not None:
+            self.n_chains = tiles[0] * ((height + 63) // 64 if wpp else tiles[1])      # fcu_tile_chains
         self.search_state = [None] * n_clips             # WPP: m_integerMv2Nx2N after each clip's last picture
         self.eng = _engine.CuEngine(width, height, max_chains=n_clips * self.n_chains, device=device)
         self.do_deblock = deblock
@@ -114,6 +129,10 @@ class LowDelayPDecider:
             kw = dict(ref=ref)
             if ref is not None and self.n_refs > 1:
                 kw = dict(refs=[self.dpb[s][q][0] for q in rl], ref_pocs=rl, poc=poc, col_ref_pocs=self.dpb[s][rl[0]][1])
+            if self.tiles is not None:
+                _, rec, out = eng.init_tile_picture(first, f, fp.qp, *self.tiles, wpp=self.wpp, params=fp, col=col, **kw)
+                res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
+                continue
             if self.wpp:
                 state = self.search_state[s] if (fp.slice_type == _engine.SLICE_P and self.slice_rows is None) else None
                 _, rec, out = eng.init_wpp_picture(first, f, fp.qp, params=fp, col=col, search_state=state, slice_rows=self.slice_rows, **kw)
@@ -132,7 +151,9 @@ class LowDelayPDecider:
             eng.compress_wpp(0, self.n_clips * self.n_chains)
             for s, r in enumerate(res):                      # HM's state after the picture: the last row's (fcu_wpp_begin_p)
                 r["search_state"] = eng.search_state(r["first"] + self.n_chains - 1)      # (sliced: the state after the last slice)
-                self.search_state[s] = r["search_state"] if self.slice_rows is None else None
+                self.search_state[s] = r["search_state"] if (self.slice_rows is None and self.tiles is None) else None
+        elif self.tiles is not None:
+            eng.compress_chains(0, self.n_clips * self.n_chains, eng.n_ctu)      # every tile to its end
         else:
             eng.compress_chains(0, self.n_clips * self.n_slices, self.slice_ctus)
         for s, r in enumerate(res):

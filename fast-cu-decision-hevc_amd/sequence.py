@@ -78,7 +78,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -87,7 +87,19 @@ class SequenceDecider:
         (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.  Cannot be combined with slice_ctus.
         slice_rows (with wpp only): WaveFrontSynchro together with SliceMode 1, SliceArgument = slice_rows x the picture width in
         CTUs -- independent slices of slice_rows whole CTU rows whose rows run as chains (fcu_wpp_begin_slices): the first row of
-        a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1)."""
+        a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1).
+        tiles=(C, R): one slice per picture cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
+        (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  Deblocking crosses the tile
+        boundaries (LFCrossTileBoundaryFlag 1).  Not with slice_ctus / slice_rows, and sao=True together with tiles is refused
+        as LowDelayPDecider refuses it (this driver runs no SAO)."""
+        sao = flags.get("sao")
+        if tiles is not None:
+            if slice_ctus or slice_rows is not None:
+                raise ValueError("SequenceDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
+            if sao:
+                raise ValueError("SequenceDecider: sao=True together with tiles is not supported (SAO merge candidates must not cross tiles; fcu_sao is not taught that)")
+            _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
+        self.tiles = tiles
         if wpp and slice_ctus:
             raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
         if slice_rows is not None and not wpp:
@@ -107,6 +119,9 @@ class SequenceDecider:
                 self.slice_mode = f"SliceMode 1, SliceArgument {slice_rows * w_ctu}"
             self.slice_mode += ", WaveFrontSynchro"
             self.n_slices = (height + 63) // 64                 # chains per picture: one per CTU row
+        if tiles is not None:
+            self.slice_mode = f"SliceMode 0 (one slice per picture), {tiles[0]} x {tiles[1]} uniform tiles" + (", WaveFrontSynchro" if wpp else "")
+            self.n_slices = tiles[0] * ((height + 63) // 64 if wpp else tiles[1])      # chains per picture (fcu_tile_chains)
         self.eng = _engine.CuEngine(width, height, max_chains=self.n_slices * self.in_flight, device=device)
         self.schedule = schedule or FastDecisionSchedule()
         self.poc = 0
@@ -135,7 +150,9 @@ class SequenceDecider:
             poc = self.poc + i
             state, sk, te = self.schedule.begin_picture(poc) if self.fast else (TRAINING, np.zeros(4, np.uint8), np.zeros(4, np.uint8))
             first = i * self.n_slices
-            if self.wpp:
+            if self.tiles is not None:
+                n_sl, rec, out = eng.init_tile_picture(first, yuv, self.qp, *self.tiles, wpp=self.wpp, **self.flags)
+            elif self.wpp:
                 n_sl, rec, out = eng.init_wpp_picture(first, yuv, self.qp, slice_rows=self.slice_rows, **self.flags)
             else:
                 n_sl, rec, out = eng.init_slice_chains(first, yuv, self.qp, self.slice_ctus, **self.flags)
@@ -147,7 +164,7 @@ class SequenceDecider:
         if self.wpp:
             eng.compress_wpp(0, len(yuvs) * self.n_slices)
         else:
-            eng.compress_chains(0, len(yuvs) * self.n_slices, self.slice_ctus)
+            eng.compress_chains(0, len(yuvs) * self.n_slices, self.slice_ctus)      # (tiles: slice_ctus = the picture, every tile runs to its end)
         nb = _engine.CTU_OUT_BYTES
         for p in pics:
             p["verify"] = eng.verify_counts(p["first"], self.n_slices) if p["state"] == VERIFYING else None

@@ -32,6 +32,10 @@
  *     (TEncSlice.cpp:1386-1411,1514-1517)            pictures in one launch, a row waiting for the row above), fcu_wpp_rows
  *     + m_integerMv2Nx2N across rows              (P: the row above's TZ start vectors, taken in the launch)
  *     (TEncSearch.cpp:3833-3842)
+ *   tiles of a one-slice picture                    fcu_tile_grid (TileUniformSpacing), fcu_tiles_begin (one chain per tile,
+ *     (TComPicSym::initTiles; TEncSlice.cpp            tile-scan order), fcu_wpp_begin_tiles (WaveFrontSynchro inside every
+ *      1386-1411,1514-1517,1718-1727;                  tile: one chain per CTU row of every tile), fcu_tile_chains
+ *      TComDataCU.cpp:422-440,1071-1390)
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -223,6 +227,42 @@ int  fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *f
  * chains than the GPU keeps resident.  Returns when the launch has finished; FCU_ERR_STATE if a row gave up waiting for the
  * row above (a bounded wait of 120 s; the pictures of the launch are then undefined). */
 int  fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream);
+/* ---- Tiles (NumTileColumnsMinus1 / NumTileRowsMinus1 with TileUniformSpacing 1; one slice per picture holding all tiles).
+ * fcu_tile_grid: TComPicSym::initTiles -- tile column i spans the CTU columns [i * W / C, (i + 1) * W / C), rows likewise; col_bd
+ * receives n_cols + 1 boundaries, row_bd n_rows + 1 (either may be NULL).  FCU_ERR_ARG for a grid with an empty tile (more columns
+ * / rows than CTU columns / rows) or a count below 1.  Pure host arithmetic.
+ * HM codes the CTUs in tile-scan order (tiles in raster order, CTUs raster inside a tile); the first CTU of every tile resets the
+ * coder; a CTU of another tile is no neighbour (intra reference samples, MPMs, split / skip contexts, spatial merge and AMVP
+ * candidates: TComDataCU::getPULeft ... getPUBelowLeft); motion vectors, the search window and motion compensation are NOT
+ * restricted to the tile; end_of_slice_segment_flag is 1 at the last CTU of the picture only.  The tiles of a picture are
+ * therefore independent chains, as slices are, and cut the picture in both directions.
+ * fcu_tiles_begin binds chains [first_chain, first_chain + n_cols * n_rows) to the tiles of ONE I or P picture (fp->slice_type),
+ * in tile-scan order; they share the planes and dev_out, and fcu_compress_chains advances them, each raster-in-tile.
+ * fcu_wpp_begin_tiles binds one chain per (tile, CTU row of the tile), tiles in tile-scan order and the rows of a tile top to
+ * bottom -- fcu_tile_chains(c, n_cols, n_rows, 1) = n_cols x the picture height in CTUs of them -- for fcu_compress_wpp: the
+ * WaveFrontSynchro rules with "first / second CTU of the row" read inside the tile (tileXPosInCtus), a one-CTU-wide tile keeps the
+ * plain reset, and a row only ever waits on the chain before it, inside its own tile.  4 x 2 uniform tiles of a 60 x 34 CTU
+ * picture: critical path 15 + 2 * 16 = 47 CTU-times instead of 60 + 2 * 33 = 126.
+ * fcu_tile_chains(c, n_cols, n_rows, wpp): chains either binding needs (-1: no such grid).
+ * FCU_ERR_ARG: fp->slice_ctus != 0 (tiles together with SliceMode 1), a grid with an empty tile, too few chains, and fp->tmvp with
+ * n_cols > 1 (HM's collocated bottom-right candidate reads across the tile edge).  Non-uniform spacing, SAO with tiles (fcu_sao's
+ * merge candidates would cross tiles), B slices, substreams and entry points are not supported; fcu_deblock runs on the whole
+ * picture as HM does with LFCrossTileBoundaryFlag 1.
+ * fcu_chain_set_decision, _set_pu_trace, fcu_get_ctx_state(_full), the reference / collocated / search-state setters (P: on EVERY
+ * chain of the picture, the same on each) work on tile chains as on slice chains.  A tile chain's position (fcu_chain_position)
+ * counts the CTUs decided INSIDE its tile; fcu_compress_ctu on a tile chain names the CTU by its picture address, in raster-in-tile
+ * order; fcu_chain_set_range on a tile chain returns FCU_ERR_STATE.
+ * The search state (m_integerMv2Nx2N) starts from zero in every tile -- this library's convention for units decided side by
+ * side; HM's tile-scan walk would carry it from the tile before, which differs only for a tile whose first CTU is too small for
+ * a 64x64 CU.  With WaveFrontSynchro it crosses the rows of a tile as it crosses the rows of a picture. */
+int  fcu_tile_grid(int width_in_ctus, int height_in_ctus, int n_cols, int n_rows, int *col_bd, int *row_bd);
+int  fcu_tile_chains(const fcu_ctx *c, int n_cols, int n_rows, int wpp);
+int  fcu_tiles_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
+                     const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
+                     uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
+int  fcu_wpp_begin_tiles(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
+                         const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
+                         uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
 /* HM-shaped call: decide CTU `ctuRsAddr` (must be the chain's next CTU) and copy its
  * TComDataCU arrays to host memory.  Synchronous. */
 int  fcu_compress_ctu(fcu_ctx *c, int chain, uint32_t ctuRsAddr, fcu_ctu_out *host_out);

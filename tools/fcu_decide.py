@@ -13,7 +13,9 @@ Slices: by default a picture is ONE slice, as in the reference's configuration (
 CTU row) per slice: a different encoder configuration (neighbourhood cut and CABAC reset at every slice start), whose
 slices are decided concurrently.  --wpp keeps one slice per picture and switches WaveFrontSynchro on (HM's WaveFrontSynchro=1):
 the CTU rows of a picture are decided concurrently, each row starting from the contexts the row above had after its second CTU
-and waiting for the row above to stay two CTUs ahead.  The slice mode is echoed on every picture line.
+and waiting for the row above to stay two CTUs ahead.  --tiles CxR keeps one slice per picture and cuts it into C x R uniform
+tiles (HM's NumTileColumnsMinus1 / NumTileRowsMinus1 with TileUniformSpacing) decided concurrently; with --wpp the CTU rows of
+every tile are decided concurrently as well.  The slice mode is echoed on every picture line.
 """
 import argparse
 import os
@@ -44,16 +46,26 @@ def main():
     ap.add_argument("--row-slices", action="store_true", help="SliceMode 1 with one CTU row per slice")
     ap.add_argument("--wpp", action="store_true", help="WaveFrontSynchro: one slice per picture, its CTU rows decided as chains that wait for the row above")
     ap.add_argument("--slice-rows", type=int, default=None, help="with --wpp: SliceMode 1 with slices of this many whole CTU rows, the rows of every slice decided as chains")
+    ap.add_argument("--tiles", default=None, metavar="CxR", help="one slice per picture cut into C x R uniform tiles decided as chains; with --wpp, WaveFrontSynchro inside every tile")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
     if args.slice_rows is not None and not args.wpp:
         ap.error("--slice-rows needs --wpp (without WaveFrontSynchro: --slice-ctus / --row-slices)")
+    tiles = None
+    if args.tiles is not None:
+        try:
+            tiles = tuple(int(v) for v in args.tiles.lower().split("x"))
+            assert len(tiles) == 2
+        except (ValueError, AssertionError):
+            ap.error("--tiles takes COLUMNSxROWS, e.g. 4x2")
+        if args.slice_ctus or args.row_slices or args.slice_rows is not None:
+            ap.error("--tiles needs one slice per picture (no --slice-ctus / --row-slices / --slice-rows)")
     import __graft_entry__ as g
     pkg = g.load_package()
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
-    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows,
+    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles,
                               schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
