@@ -202,4 +202,27 @@ inline int tile_ctu_addr(const Chain &h, int pos) { return (h.tile_y0 + pos / h.
 inline bool tile_is_picture(const Chain &h) { return h.tile_x0 == 0 && h.tile_y0 == 0 && h.tile_w == h.w_ctu && h.tile_h == h.h_ctu; }
 inline bool tile_is_last(const Chain &h) { return h.tile_x0 + h.tile_w == h.w_ctu && h.tile_y0 + h.tile_h == h.h_ctu; }
 
+/* ---- the tile grid as the loop-filter kernels take it (fcu_deblock_tiles / fcu_sao_tiles), by value in the kernel arguments:
+ * bit i of col / row = CTU column / row i is the first of a tile (bit 0 always), cross = LFCrossTileBoundaryFlag.  Two bitmasks
+ * and no pointer: the kernels ask "does this CTU column / row start a tile" and nothing else, so another spacing rule is a change
+ * of lf_tiles_fill alone.  256 bits each: pictures up to 256 x 256 CTUs (sao_decide's ring already ends at 255 columns). */
+enum { LF_TILE_WORDS = 4, LF_TILE_MAX_CTUS = 64 * LF_TILE_WORDS };
+struct LfTiles { uint64_t col[LF_TILE_WORDS], row[LF_TILE_WORDS]; int32_t cross, pad; };
+/* false = no such grid (tile_grid), a picture beyond 256 CTUs in either direction, or a flag outside {0, 1} */
+inline bool lf_tiles_fill(LfTiles &T, int W, int H, int n_cols, int n_rows, int cross)
+{
+  if (!tile_grid(W, H, n_cols, n_rows, nullptr, nullptr) || W > LF_TILE_MAX_CTUS || H > LF_TILE_MAX_CTUS || (cross != 0 && cross != 1)) return false;
+  for (int k = 0; k < LF_TILE_WORDS; k++) { T.col[k] = 0; T.row[k] = 0; }
+  for (int i = 0; i < n_cols; i++) { const int b = (int)((long long)i * W / n_cols); T.col[b >> 6] |= (uint64_t)1 << (b & 63); }
+  for (int i = 0; i < n_rows; i++) { const int b = (int)((long long)i * H / n_rows); T.row[b >> 6] |= (uint64_t)1 << (b & 63); }
+  T.cross = cross; T.pad = 0;
+  return true;
+}
+/* does CTU column / row i start a tile?  The word is picked by selects, not by an address: the masks stay in registers. */
+FCU_DEV int lf_tile_start(const uint64_t *m, int i)
+{
+  const uint64_t w = i < 64 ? m[0] : (i < 128 ? m[1] : (i < 192 ? m[2] : m[3]));
+  return (int)((w >> (i & 63)) & 1u);
+}
+
 } // namespace fcu

@@ -743,11 +743,24 @@ int fcu_obf_prepass(fcu_ctx *c, int n_frames, const uint8_t *dev_y, int16_t *dev
   return FCU_OK;
 }
 
-int fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
-                int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream)
+} /* extern "C" */
+
+/* the grid of fcu_deblock_tiles / fcu_sao_tiles as the kernels take it; FCU_ERR_ARG with the entry point's name */
+static int lf_tiles_arg(const fcu_ctx *c, int n_cols, int n_rows, int lf_cross_tiles, const char *name, LfTiles &T)
 {
-  if (!c || !dev_out || !dev_rec_y || !dev_rec_u || !dev_rec_v) return fail(FCU_ERR_ARG, "fcu_deblock: bad argument");
-  if (beta_offset_div2 < -6 || beta_offset_div2 > 6 || tc_offset_div2 < -6 || tc_offset_div2 > 6) return fail(FCU_ERR_ARG, "fcu_deblock: offsets are limited to [-6, 6]");
+  if (lf_cross_tiles != 0 && lf_cross_tiles != 1) return fail(FCU_ERR_ARG, std::string(name) + ": lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1");
+  const int W = (c->sp.width + 63) / 64, H = (c->sp.height + 63) / 64;
+  if (!tile_grid(W, H, n_cols, n_rows, nullptr, nullptr)) return fail(FCU_ERR_ARG, std::string(name) + ": a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
+  if (!lf_tiles_fill(T, W, H, n_cols, n_rows, lf_cross_tiles)) return fail(FCU_ERR_ARG, std::string(name) + ": pictures beyond 256 CTUs in width or height are not supported with tiles");
+  return FCU_OK;
+}
+
+/* fcu_deblock (T null: the kernels without a grid) and fcu_deblock_tiles */
+static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                       int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream)
+{
+  if (!dev_out || !dev_rec_y || !dev_rec_u || !dev_rec_v) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
+  if (beta_offset_div2 < -6 || beta_offset_div2 > 6 || tc_offset_div2 < -6 || tc_offset_div2 > 6) return fail(FCU_ERR_ARG, std::string(name) + ": offsets are limited to [-6, 6]");
   HIPCHK(hipSetDevice(c->sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
   const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64;
@@ -756,10 +769,13 @@ int fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint
   struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
   if (kernel_ms2) { for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
   /* all vertical edges of the picture before the first horizontal one (TComLoopFilter.cpp:133-154): stream order */
-  hipLaunchKernelGGL(dbk_pass<0>, dim3((n0 + DBK_THREADS - 1) / DBK_THREADS), dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2);
+  const dim3 g0((n0 + DBK_THREADS - 1) / DBK_THREADS), g1((n1 + DBK_THREADS - 1) / DBK_THREADS);
+  if (T) hipLaunchKernelGGL((dbk_pass<0, true>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
+  else hipLaunchKernelGGL((dbk_pass<0, false>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
   HIPCHK(hipGetLastError());
   if (kernel_ms2) HIPCHK(hipEventRecord(e[1], st));
-  hipLaunchKernelGGL(dbk_pass<1>, dim3((n1 + DBK_THREADS - 1) / DBK_THREADS), dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2);
+  if (T) hipLaunchKernelGGL((dbk_pass<1, true>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
+  else hipLaunchKernelGGL((dbk_pass<1, false>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
   HIPCHK(hipGetLastError());
   if (kernel_ms2) {
     HIPCHK(hipEventRecord(e[2], st));
@@ -769,20 +785,23 @@ int fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint
   return FCU_OK;
 }
 
-int fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
-            fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
+/* fcu_sao (T null: the kernels without a grid) and fcu_sao_tiles */
+static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
+                   fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
 {
-  if (!c || n_pics <= 0 || !params || !dev_org || !dev_rec || !dev_coded) return fail(FCU_ERR_ARG, "fcu_sao: bad argument");
-  for (int i = 0; i < 3 * n_pics; i++) if (!dev_org[i] || !dev_rec[i]) return fail(FCU_ERR_ARG, "fcu_sao: null plane");
+  const std::string name(name_);
+  if (n_pics <= 0 || !params || !dev_org || !dev_rec || !dev_coded) return fail(FCU_ERR_ARG, name + ": bad argument");
+  for (int i = 0; i < 3 * n_pics; i++) if (!dev_org[i] || !dev_rec[i]) return fail(FCU_ERR_ARG, name + ": null plane");
   for (int i = 0; i < n_pics; i++) {
-    if (params[i].slice_type != FCU_SLICE_I && params[i].slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, "fcu_sao: slice type");
-    if (params[i].qp < 0 || params[i].qp > 51 || params[i].slice_ctus < 0) return fail(FCU_ERR_ARG, "fcu_sao: qp / slice_ctus");
-    if (!(params[i].lambda[0] > 0) || params[i].lambda[1] < 0 || params[i].lambda[2] < 0) return fail(FCU_ERR_ARG, "fcu_sao: lambda[0] must be positive");
+    if (params[i].slice_type != FCU_SLICE_I && params[i].slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, name + ": slice type");
+    if (params[i].qp < 0 || params[i].qp > 51 || params[i].slice_ctus < 0) return fail(FCU_ERR_ARG, name + ": qp / slice_ctus");
+    if (T && params[i].slice_ctus != 0) return fail(FCU_ERR_ARG, name + ": tiles need one slice per picture (slice_ctus 0)");
+    if (!(params[i].lambda[0] > 0) || params[i].lambda[1] < 0 || params[i].lambda[2] < 0) return fail(FCU_ERR_ARG, name + ": lambda[0] must be positive");
   }
   HIPCHK(hipSetDevice(c->sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
   const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64, n_ctu = c->n_ctu;
-  if (w_ctu + 1 > SAO_RING) return fail(FCU_ERR_ARG, "fcu_sao: pictures wider than 255 CTUs are not supported (sao_decide's neighbour ring)");
+  if (w_ctu + 1 > SAO_RING) return fail(FCU_ERR_ARG, name + ": pictures wider than 255 CTUs are not supported (sao_decide's neighbour ring)");
   const size_t plane[3] = { (size_t)w * h, (size_t)(w / 2) * (h / 2), (size_t)(w / 2) * (h / 2) }, pic_bytes = plane[0] + 2 * plane[1];
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_pics = 0, o_src = up(o_pics + sizeof(SaoPic) * n_pics), o_stats = up(o_src + pic_bytes * n_pics),
@@ -814,23 +833,62 @@ int fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t 
   hipEvent_t e[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
   struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 5; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
   if (kernel_ms4) { for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
-  hipLaunchKernelGGL(sao_stats, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu);
+  if (T) hipLaunchKernelGGL(sao_stats_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu, *T);
+  else hipLaunchKernelGGL(sao_stats, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
   if (kernel_ms4) HIPCHK(hipEventRecord(e[1], st));
   const long long n_cand = (long long)n_pics * n_ctu * 15;
   hipLaunchKernelGGL(sao_cands, dim3((unsigned)((n_cand + SAO_THREADS - 1) / SAO_THREADS)), dim3(SAO_THREADS), 0, st, d_pics, d_stats, d_cand, n_ctu, n_pics);
   HIPCHK(hipGetLastError());
   if (kernel_ms4) HIPCHK(hipEventRecord(e[2], st));
-  hipLaunchKernelGGL(sao_decide, dim3(n_pics), dim3(64), 0, st, d_pics, d_stats, d_cand, dev_coded, d_recon, d_off, w_ctu, n_ctu, n_pics);
+  if (T) hipLaunchKernelGGL(sao_decide_tiles, dim3(n_pics), dim3(64), 0, st, d_pics, d_stats, d_cand, dev_coded, d_recon, d_off, w_ctu, n_ctu, n_pics, *T);
+  else hipLaunchKernelGGL(sao_decide, dim3(n_pics), dim3(64), 0, st, d_pics, d_stats, d_cand, dev_coded, d_recon, d_off, w_ctu, n_ctu, n_pics);
   HIPCHK(hipGetLastError());
   if (kernel_ms4) HIPCHK(hipEventRecord(e[3], st));
-  hipLaunchKernelGGL(sao_apply, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu);
+  if (T) hipLaunchKernelGGL(sao_apply_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu, *T);
+  else hipLaunchKernelGGL(sao_apply, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
   if (kernel_ms4) HIPCHK(hipEventRecord(e[4], st));
   if (off_count) HIPCHK(hipMemcpyAsync(off_count, d_off, sizeof(int32_t) * 3 * n_pics, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and off_count are done with */
   if (kernel_ms4) for (int i = 0; i < 4; i++) hipEventElapsedTime(&kernel_ms4[i], e[i], e[i + 1]);
   return FCU_OK;
+}
+
+extern "C" {
+
+int fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_deblock: bad argument");
+  return deblock_run(c, "fcu_deblock", nullptr, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
+}
+
+int fcu_deblock_tiles(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                      int beta_offset_div2, int tc_offset_div2, int n_cols, int n_rows, int lf_cross_tiles, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_deblock_tiles: bad argument");
+  LfTiles T;
+  const int rc = lf_tiles_arg(c, n_cols, n_rows, lf_cross_tiles, "fcu_deblock_tiles", T);
+  if (rc != FCU_OK) return rc;
+  return deblock_run(c, "fcu_deblock_tiles", &T, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
+}
+
+int fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
+            fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_sao: bad argument");
+  return sao_run(c, "fcu_sao", nullptr, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
+}
+
+int fcu_sao_tiles(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int n_cols, int n_rows, int lf_cross_tiles,
+                  const uint8_t *const *dev_org, uint8_t *const *dev_rec, fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_sao_tiles: bad argument");
+  LfTiles T;
+  const int rc = lf_tiles_arg(c, n_cols, n_rows, lf_cross_tiles, "fcu_sao_tiles", T);
+  if (rc != FCU_OK) return rc;
+  return sao_run(c, "fcu_sao_tiles", &T, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
 }
 
 void fcu_sao_enabled(const double rate[3][8], int layer, int32_t enabled[3])

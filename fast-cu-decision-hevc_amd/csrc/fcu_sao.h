@@ -17,8 +17,13 @@
  *                choice, and the reconstruction of merged parameters (see sao_decide_picture below).
  *   sao_apply    one workgroup per (CTU, component, picture): offsetBlock (:317-556) from the untouched copy of the
  *                deblocked picture into the reconstruction.  HBM-bound: reads src, writes rec.
- * 8-bit 4:2:0, 64x64 CTUs, LFCrossSliceBoundaryFlag 1, no tiles: neighbour availability is the picture boundary
- * (TComPicSym.cpp:357-376); merge candidates stay inside the CTU's slice (TComPic.cpp:138-143).
+ * 8-bit 4:2:0, 64x64 CTUs, LFCrossSliceBoundaryFlag 1.  Without tiles neighbour availability is the picture boundary
+ * (TComPicSym.cpp:357-376) and merge candidates stay inside the CTU's slice (TComPic.cpp:138-143).
+ * Tiles (fcu_sao_tiles) are a compile-time variant of the kernel bodies, TILES = true, which takes the grid (LfTiles, fcu_host.h)
+ * by value: a merge candidate must lie in the CTU's tile (TComPic.cpp:138-143) whatever LFCrossTileBoundaryFlag says, and with
+ * the flag 0 a CTU of another tile is unavailable to the statistics and the offset pass in all eight directions
+ * (deriveLoopFilterBoundaryAvailibility, TComPicSym.cpp:378,449-459).  decideBlkParams still walks the picture in raster order and
+ * carries the coder across tile boundaries.  TILES = false is the code as it was: the kernels fcu_sao launches do not change.
  * Algorithmic bytes per picture: stats 2 x 1.5 W H read; apply 1.5 W H read + <= 1.5 W H written.
  */
 #pragma once
@@ -37,8 +42,15 @@ struct SaoCand { int16_t aux, ep; int32_t off[5]; long long dist; };   /* EO: of
 __device__ static inline int sao_sgn(int v) { return (v > 0) - (v < 0); }
 
 /* ---- statistics: phase 0 clears the histogram, 1 accumulates, 2 writes it out -------------------------------------- */
-template <int PHASE>
-__device__ static inline void sao_stats_phase(int32_t *hist, const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu)
+/* L / R / A / B of CTU (cx, cy) with LFCrossTileBoundaryFlag 0: a CTU of another tile is no neighbour.  Wave-uniform. */
+__device__ static inline void sao_tile_avail(const LfTiles &T, int cx, int cy, int &L, int &R, int &A, int &B)
+{
+  if (T.cross) return;
+  L = L && !lf_tile_start(T.col, cx); R = R && !lf_tile_start(T.col, cx + 1);
+  A = A && !lf_tile_start(T.row, cy); B = B && !lf_tile_start(T.row, cy + 1);
+}
+template <int PHASE, bool TILES = false>
+__device__ static inline void sao_stats_phase(int32_t *hist, const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu, const LfTiles &T = LfTiles())
 {
   const int t = (int)threadIdx.x, a = (int)blockIdx.x, comp = (int)blockIdx.y, pic = (int)blockIdx.z;
   if (PHASE == 0) { for (int i = t; i < SAO_STAT_INTS; i += SAO_THREADS) hist[i] = 0; return; }
@@ -46,7 +58,9 @@ __device__ static inline void sao_stats_phase(int32_t *hist, const SaoPic *pics,
   const SaoPic &P = pics[pic];
   const int sh = comp ? 1 : 0, cx = a % w_ctu, cy = a / w_ctu, x0 = cx * 64, y0 = cy * 64;
   const int bw = (x0 + 64 > width ? width - x0 : 64) >> sh, bh = (y0 + 64 > height ? height - y0 : 64) >> sh, stride = width >> sh;
-  const int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height, AL = A && L;
+  int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height;
+  if (TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
+  const int AL = A && L;
   const int skipR = comp ? 3 : 5, skipB = comp ? 2 : 4;
   const int sx = L ? 0 : 1, ex = R ? bw - skipR : bw - 1, exFull = R ? bw - skipR : bw;
   const int eyFull = B ? bh - skipB : bh, ey = B ? bh - skipB : bh - 1;
@@ -283,6 +297,9 @@ struct SaoNb { int left, above; };                         /* merge candidates: 
  *                 coder chroma starts from depends on luma only through the sao_type_idx bin luma coded -- the counter is
  *                 reset to its Q15 remainder, which whole bypass bins do not change -- so there are two cases, not six;
  *   lanes 32..37  distortion of the left / above CTU's parameters on this CTU's statistics, per component (:760-766). */
+/* (TILES does nothing in sao_ctu_costs / sao_ctu_choose: it gives each kernel variant its own copy, so that sao_decide sees the
+ * call graph it had -- one caller per helper -- and comes out of the inliner as it did) */
+template <bool TILES>
 __device__ static inline void sao_ctu_costs(int lane, SaoDecideLds &L, const int32_t *st, const SaoCand *cd, int a, int w_ctu, const SaoNb nb)
 {
   const int en0 = L.en[0], en1 = L.en[1], en2 = L.en[2];
@@ -332,6 +349,7 @@ __device__ static inline void sao_ctu_costs(int lane, SaoDecideLds &L, const int
   }
 }
 /* Second half, lane 0: the choices in the reference's order, the coder after the CTU, the CTU's reconstructed parameters */
+template <bool TILES>
 __device__ static inline void sao_ctu_choose(SaoDecideLds &L, const SaoCand *cd, int a, int w_ctu, const SaoNb nb)
 {
   const int en0 = L.en[0], en1 = L.en[1], en2 = L.en[2];
@@ -394,8 +412,9 @@ __device__ static inline void sao_ctu_choose(SaoDecideLds &L, const SaoCand *cd,
 }
 /* coded[] = parameters as signalled, recon[] = after reconstructBlkSAOParam, off_count[comp] = CTUs whose reconstructed mode is
  * OFF (-> m_saoDisabledRate) */
+template <bool TILES = false>
 __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t *stats, const SaoCand *cands, fcu_sao_ctu *coded, fcu_sao_ctu *recon,
-                                                 int32_t *off_count, int w_ctu, int n_ctu, SaoDecideLds &L)
+                                                 int32_t *off_count, int w_ctu, int n_ctu, SaoDecideLds &L, const LfTiles &T = LfTiles())
 {
   const int slice_ctus = P_.slice_ctus;                      /* the descriptor lives in HBM: read once, not per CTU behind the record stores */
   int32_t pre[SAO_NL][SAO_PRE];
@@ -416,10 +435,11 @@ __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t
     SAO_PHASE { if (a + 1 < n_ctu) sao_fetch(lane, stats, cands, a + 1, pre[SAO_L]); }
     if (slice_ctus > 0 && a == sliceStart + slice_ctus) sliceStart = a;
     SaoNb nb; nb.above = cy > 0 && a - w_ctu >= sliceStart; nb.left = cx > 0 && a - 1 >= sliceStart;
+    if (TILES) { nb.above = nb.above && !lf_tile_start(T.row, cy); nb.left = nb.left && !lf_tile_start(T.col, cx); }      /* the candidate's tile: either value of the flag */
     if (++cx == w_ctu) { cx = 0; cy++; }
-    SAO_PHASE { sao_ctu_costs(lane, L, L.stats[a & 1], L.cand[a & 1], a, w_ctu, nb); }
+    SAO_PHASE { sao_ctu_costs<TILES>(lane, L, L.stats[a & 1], L.cand[a & 1], a, w_ctu, nb); }
     SAO_SYNC();
-    SAO_PHASE { if (lane == 0) sao_ctu_choose(L, L.cand[a & 1], a, w_ctu, nb); }
+    SAO_PHASE { if (lane == 0) sao_ctu_choose<TILES>(L, L.cand[a & 1], a, w_ctu, nb); }
     SAO_PHASE { if (a + 1 < n_ctu) sao_stash(lane, pre[SAO_L], L.stats[(a + 1) & 1], L.cand[(a + 1) & 1]); }
     SAO_SYNC();
     SAO_PHASE {                                               /* the CTU's two records, a dword per lane */
@@ -437,7 +457,8 @@ __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t
 }
 
 /* ---- offsetBlock, TComSampleAdaptiveOffset.cpp:317-556 -------------------------------------------------------------- */
-__device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu)
+template <bool TILES = false>
+__device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu, const LfTiles &T = LfTiles())
 {
   const int t = (int)threadIdx.x, a = (int)blockIdx.x, comp = (int)blockIdx.y, pic = (int)blockIdx.z;
   const fcu_sao_offset &p = recon[(size_t)pic * n_ctu + a].c[comp];
@@ -445,7 +466,9 @@ __device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_
   const SaoPic &P = pics[pic];
   const int sh = comp ? 1 : 0, cx = a % w_ctu, cy = a / w_ctu, x0 = cx * 64, y0 = cy * 64;
   const int w = (x0 + 64 > width ? width - x0 : 64) >> sh, h = (y0 + 64 > height ? height - y0 : 64) >> sh, stride = width >> sh;
-  const int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height, AL = A && L, AR = A && R, BL = B && L, BR = B && R;
+  int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height;
+  if (TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
+  const int AL = A && L, AR = A && R, BL = B && L, BR = B && R;
   const int sx = L ? 0 : 1, ex = R ? w : w - 1, type = p.type;
   const size_t o0 = (size_t)(y0 >> sh) * stride + (x0 >> sh);
   const uint8_t *src = P.src[comp] + o0; uint8_t *res = P.rec[comp] + o0;
@@ -495,6 +518,26 @@ __global__ void __launch_bounds__(64) sao_decide(const SaoPic *pics, const int32
 }
 __global__ void __launch_bounds__(SAO_THREADS) sao_apply(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu)
 { sao_apply_block(pics, recon, width, height, w_ctu, n_ctu); }
+/* the tile variants fcu_sao_tiles launches (sao_cands knows no neighbours and serves both) */
+__global__ void __launch_bounds__(SAO_THREADS) sao_stats_tiles(const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu, LfTiles T)
+{
+  __shared__ int32_t hist[SAO_STAT_INTS];
+  sao_stats_phase<0, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+  __syncthreads();
+  sao_stats_phase<1, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+  __syncthreads();
+  sao_stats_phase<2, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+}
+__global__ void __launch_bounds__(64) sao_decide_tiles(const SaoPic *pics, const int32_t *stats, const SaoCand *cands, fcu_sao_ctu *coded, fcu_sao_ctu *recon,
+                                                       int32_t *off_count, int w_ctu, int n_ctu, int n_pics, LfTiles T)
+{
+  __shared__ SaoDecideLds L;
+  const int pic = (int)blockIdx.x;
+  sao_decide_picture<true>(pics[pic], stats + (size_t)pic * n_ctu * 3 * SAO_STAT_INTS, cands + (size_t)pic * n_ctu * 15,
+                           coded + (size_t)pic * n_ctu, recon + (size_t)pic * n_ctu, off_count + pic * 3, w_ctu, n_ctu, L, T);
+}
+__global__ void __launch_bounds__(SAO_THREADS) sao_apply_tiles(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu, LfTiles T)
+{ sao_apply_block<true>(pics, recon, width, height, w_ctu, n_ctu, T); }
 #endif
 
 } /* namespace fcu */

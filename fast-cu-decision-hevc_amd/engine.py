@@ -88,7 +88,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
-           "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles"]
+           "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -155,6 +155,8 @@ def load_lib():
     lib.fcu_frame_state.argtypes = [C.c_int] * 4
     lib.fcu_deblock.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_sao.argtypes = [C.c_void_p, C.c_int, C.POINTER(SaoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_deblock_tiles.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_sao_tiles.argtypes = [C.c_void_p, C.c_int, C.POINTER(SaoParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_sao_enabled.restype = None
     lib.fcu_sao_enabled.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.fcu_sao_update_rate.restype = None
@@ -569,24 +571,33 @@ class CuEngine:
         return trace.cpu().numpy().view(PU_TRACE_DTYPE).reshape(self.n_ctu, PUS_PER_CTU)
 
     # -- TComLoopFilter::loopFilterPic
-    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None):
+    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1):
         """Deblocks, in place, the reconstruction planes bound to `chain` (all slice chains of a picture share them)
         once every CTU of the picture has been decided -- or explicit device tensors: `out` = the picture's
-        fcu_ctu_out array as uint8, `rec` = (Y, U, V).  Returns (ms vertical pass, ms horizontal pass) if timed."""
+        fcu_ctu_out array as uint8, `rec` = (Y, U, V).  tiles=(C, R): the picture's uniform tile grid, filtered with
+        LFCrossTileBoundaryFlag = lf_cross_tiles (fcu_deblock_tiles; 0 leaves the tile boundaries unfiltered); without tiles
+        lf_cross_tiles is not looked at.  Returns (ms vertical pass, ms horizontal pass) if timed."""
         if chain is not None:
             _, rec, out = self._keep[chain]
         assert out.numel() >= self.n_ctu * CTU_OUT_BYTES and rec[0].numel() == self.width * self.height
         ms = (C.c_float * 2)() if timed else None
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        self._chk(self.lib.fcu_deblock(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
-                                       beta_offset_div2, tc_offset_div2, ms, s), "fcu_deblock")
+        if tiles is not None:
+            self._chk(self.lib.fcu_deblock_tiles(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
+                                                 beta_offset_div2, tc_offset_div2, int(tiles[0]), int(tiles[1]), int(lf_cross_tiles), ms, s), "fcu_deblock_tiles")
+        else:
+            self._chk(self.lib.fcu_deblock(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
+                                           beta_offset_div2, tc_offset_div2, ms, s), "fcu_deblock")
         return (ms[0], ms[1]) if timed else None
 
     # -- TEncSampleAdaptiveOffset::SAOProcess
-    def sao(self, pictures, timed=False, stream=None):
+    def sao(self, pictures, timed=False, stream=None, tiles=None, lf_cross_tiles=1):
         """SAO of completely decided, deblocked pictures, in place on their reconstruction planes.  pictures: list of dicts
         {org: (Y,U,V) device tensors, rec: (Y,U,V) device tensors, qp, lambda_ (the slice's luma lambda), slice_type,
-        slice_ctus, enabled (3 ints, default all on), chroma_weight (default: from the QP, chroma QP offset 0)}.  Returns (coded uint8 tensor
+        slice_ctus, enabled (3 ints, default all on), chroma_weight (default: from the QP, chroma QP offset 0)}.
+        tiles=(C, R): every picture of the batch is cut into C x R uniform tiles (fcu_sao_tiles): merge candidates stay inside
+        the CTU's tile, and with lf_cross_tiles=0 (LFCrossTileBoundaryFlag) so do the samples the statistics and the offset pass
+        read; slice_ctus must then be 0.  Returns (coded uint8 tensor
         [n, n_ctu, SAO_CTU_BYTES] on the device, off_count int32 array [n, 3], kernel ms x4 or None)."""
         torch = self.torch
         n = len(pictures)
@@ -607,7 +618,10 @@ class CuEngine:
         off = np.zeros((n, 3), np.int32)
         ms = (C.c_float * 4)() if timed else None
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        self._chk(self.lib.fcu_sao(self.h, n, prm, org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao")
+        if tiles is not None:
+            self._chk(self.lib.fcu_sao_tiles(self.h, n, prm, int(tiles[0]), int(tiles[1]), int(lf_cross_tiles), org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao_tiles")
+        else:
+            self._chk(self.lib.fcu_sao(self.h, n, prm, org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao")
         return coded, off, (list(ms) if timed else None)
 
     # -- TEncCu::destroy

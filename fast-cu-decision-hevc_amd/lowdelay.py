@@ -6,7 +6,8 @@ Pictures of ONE clip are strictly sequential (every P picture needs the filtered
 the parallelism of a launch comes from the slices of a picture and from independent clips side by side: clip s, slice k
 is chain s * n_slices + k.  Per picture: fcu_ldp_slice (QP / lambda of HM's lowdelay_P GOP table) -> fcu_chain_begin
 (+ fcu_chain_set_reference for P) -> one fcu_compress_chains launch over all chains -> fcu_deblock -> fcu_sao (SAO 1, the
-reference's lowdelay configuration; one batched call for all clips) -> fcu_pad_reference.
+reference's lowdelay configuration; one batched call for all clips) -> fcu_pad_reference.  A picture with tiles goes through
+fcu_deblock_tiles / fcu_sao_tiles instead, with the LFCrossTileBoundaryFlag the caller chose.
 Across GPUs the reference picture is the only data a rank would need from another one (one copy per picture, SURVEY.md 8e);
 with whole clips per rank there is none.
 
@@ -56,22 +57,30 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
         (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles: one chain per CTU row of every
-        tile).  Every tile of every picture starts from a zero search state.  Not with slice_ctus / slice_rows, not with sao, and
-        not with tmvp when C > 1."""
+        tile).  Every tile of every picture starts from a zero search state.  Not with slice_ctus / slice_rows, and not with tmvp
+        when C > 1.
+        lf_cross_tiles (with tiles only): LFCrossTileBoundaryFlag of the loop filters, 0 or 1 -- whether deblocking filters the
+        tile boundaries and SAO reads samples across them (fcu_deblock_tiles / fcu_sao_tiles).  None means 1 for deblocking,
+        HM's default; sao=True together with tiles asks for an explicit choice."""
         if tiles is not None:
             if slice_ctus or slice_rows is not None:
                 raise ValueError("LowDelayPDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
-            if sao:
-                raise ValueError("LowDelayPDecider: sao=True together with tiles is not supported (SAO merge candidates must not cross tiles; fcu_sao is not taught that)")
+            if lf_cross_tiles is not None and lf_cross_tiles not in (0, 1):
+                raise ValueError("LowDelayPDecider: lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1")
+            if sao and lf_cross_tiles is None:
+                raise ValueError("LowDelayPDecider: sao=True together with tiles needs lf_cross_tiles=0 or 1 (LFCrossTileBoundaryFlag: whether SAO and deblocking reach across the tile boundaries)")
             _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
             if tmvp and tiles[0] > 1:
                 raise ValueError("LowDelayPDecider: tmvp together with tile columns is not supported (the collocated bottom-right candidate reads across the tile edge)")
+        elif lf_cross_tiles is not None:
+            raise ValueError("LowDelayPDecider: lf_cross_tiles is the loop filters' flag of a picture with tiles and needs tiles=(C, R)")
         self.tiles = tiles
+        self.lf_cross_tiles = 1 if lf_cross_tiles is None else lf_cross_tiles
         if wpp and slice_ctus:
             raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
         if slice_rows is not None and not wpp:
@@ -159,12 +168,12 @@ class LowDelayPDecider:
         for s, r in enumerate(res):
             r["rec_unfiltered"] = [p.clone() for p in r["rec"]]
             if self.do_deblock:
-                eng.deblock(r["first"])
+                eng.deblock(r["first"], tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
         if self.do_sao:
             layer = _engine.ldp_layer(poc)
             pics = [{"org": eng._keep[r["first"]][0], "rec": r["rec"], "qp": fp.qp, "lambda_": fp.lambda_, "slice_type": fp.slice_type,
                      "slice_ctus": self.sao_slice_ctus, "enabled": self.sao_rate[s].enabled(layer)} for s, r in enumerate(res)]
-            coded, off, _ = eng.sao(pics)
+            coded, off, _ = eng.sao(pics, tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
             for s, r in enumerate(res):
                 r["sao"], r["sao_enabled"] = coded[s], pics[s]["enabled"]
                 self.sao_rate[s].update(layer, off[s], eng.n_ctu)

@@ -78,7 +78,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -89,17 +89,25 @@ class SequenceDecider:
         CTUs -- independent slices of slice_rows whole CTU rows whose rows run as chains (fcu_wpp_begin_slices): the first row of
         a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1).
         tiles=(C, R): one slice per picture cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
-        (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  Deblocking crosses the tile
-        boundaries (LFCrossTileBoundaryFlag 1).  Not with slice_ctus / slice_rows, and sao=True together with tiles is refused
-        as LowDelayPDecider refuses it (this driver runs no SAO)."""
+        (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  lf_cross_tiles (with tiles
+        only): LFCrossTileBoundaryFlag of the deblocking, 0 or 1 (fcu_deblock_tiles); None means 1, HM's default -- deblocking
+        crosses the tile boundaries.  Not with slice_ctus / slice_rows.  This driver runs no SAO: sao=True together with
+        tiles is refused whatever lf_cross_tiles says."""
         sao = flags.get("sao")
         if tiles is not None:
             if slice_ctus or slice_rows is not None:
                 raise ValueError("SequenceDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
+            if lf_cross_tiles is not None and lf_cross_tiles not in (0, 1):
+                raise ValueError("SequenceDecider: lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1")
+            if sao and lf_cross_tiles is None:
+                raise ValueError("SequenceDecider: sao=True together with tiles needs lf_cross_tiles=0 or 1 -- and this driver runs no SAO (LowDelayPDecider does)")
             if sao:
-                raise ValueError("SequenceDecider: sao=True together with tiles is not supported (SAO merge candidates must not cross tiles; fcu_sao is not taught that)")
+                raise ValueError("SequenceDecider: sao=True is not supported: this driver runs no SAO (LowDelayPDecider(tiles=..., sao=True, lf_cross_tiles=...) does)")
             _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
+        elif lf_cross_tiles is not None:
+            raise ValueError("SequenceDecider: lf_cross_tiles is the deblocking flag of a picture with tiles and needs tiles=(C, R)")
         self.tiles = tiles
+        self.lf_cross_tiles = 1 if lf_cross_tiles is None else lf_cross_tiles
         if wpp and slice_ctus:
             raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
         if slice_rows is not None and not wpp:
@@ -171,7 +179,7 @@ class SequenceDecider:
             if self.fast:
                 self.schedule.end_picture(p["poc"], p["verify"])
             if self.do_deblock:
-                eng.deblock(p["first"])
+                eng.deblock(p["first"], tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
         eng.sync()
         for p in pics:
             p["depth"] = p["out"].view(eng.n_ctu, nb)[:, :256].cpu().numpy().copy()      # fcu_ctu_out.depth leads the struct

@@ -22,11 +22,13 @@
  *      tools_YS.cpp:686-695,968-986,1123-1154,1237)   (getCurrentState)
  *   TEncSearch::estIntraPredLumaQT per-PU results  fcu_chain_set_pu_trace (BASELINE configs[1]: luma RDO artefact)
  *     (TEncSearch.cpp:2178-2655)
- *   TComLoopFilter::loopFilterPic                  fcu_deblock (in-loop deblocking of the decided picture)
- *     (TComLoopFilter.cpp:130, TEncGOP.cpp:1160)
+ *   TComLoopFilter::loopFilterPic                  fcu_deblock (in-loop deblocking of the decided picture);
+ *     (TComLoopFilter.cpp:130, TEncGOP.cpp:1160)     a picture with tiles: fcu_deblock_tiles (LFCrossTileBoundaryFlag 0 or 1)
  *   TEncSampleAdaptiveOffset::SAOProcess           fcu_sao (statistics, per-CTU parameter decision, offset pass) +
  *     (TEncSampleAdaptiveOffset.cpp:257,              fcu_sao_enabled / fcu_sao_update_rate (decidePicParams and the
- *      TEncGOP.cpp:1427-1441)                         m_saoDisabledRate bookkeeping across pictures, :363-395,895-917)
+ *      TEncGOP.cpp:1427-1441)                         m_saoDisabledRate bookkeeping across pictures, :363-395,895-917);
+ *                                                    a picture with tiles: fcu_sao_tiles (merge candidates inside the tile,
+ *                                                    TComPic.cpp:138-143; LFCrossTileBoundaryFlag 0 or 1, TComPicSym.cpp:378,449-459)
  *   WaveFrontSynchro=1 row loop of                 fcu_wpp_begin / fcu_wpp_begin_p (one chain per CTU row of a
  *     TEncSlice::compressSlice                       one-slice I / P picture), fcu_compress_wpp (every row of whole
  *     (TEncSlice.cpp:1386-1411,1514-1517)            pictures in one launch, a row waiting for the row above), fcu_wpp_rows
@@ -245,9 +247,10 @@ int  fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream);
  * picture: critical path 15 + 2 * 16 = 47 CTU-times instead of 60 + 2 * 33 = 126.
  * fcu_tile_chains(c, n_cols, n_rows, wpp): chains either binding needs (-1: no such grid).
  * FCU_ERR_ARG: fp->slice_ctus != 0 (tiles together with SliceMode 1), a grid with an empty tile, too few chains, and fp->tmvp with
- * n_cols > 1 (HM's collocated bottom-right candidate reads across the tile edge).  Non-uniform spacing, SAO with tiles (fcu_sao's
- * merge candidates would cross tiles), B slices, substreams and entry points are not supported; fcu_deblock runs on the whole
- * picture as HM does with LFCrossTileBoundaryFlag 1.
+ * n_cols > 1 (HM's collocated bottom-right candidate reads across the tile edge).  Non-uniform spacing, tiles together with
+ * SliceMode 1, B slices, substreams and entry points are not supported.  The loop filters of a tile picture are fcu_deblock_tiles
+ * and fcu_sao_tiles below (fcu_deblock is the deblocking of LFCrossTileBoundaryFlag 1; fcu_sao's merge candidates would cross
+ * tiles).
  * fcu_chain_set_decision, _set_pu_trace, fcu_get_ctx_state(_full), the reference / collocated / search-state setters (P: on EVERY
  * chain of the picture, the same on each) work on tile chains as on slice chains.  A tile chain's position (fcu_chain_position)
  * counts the CTUs decided INSIDE its tile; fcu_compress_ctu on a tile chain names the CTU by its picture address, in raster-in-tile
@@ -317,14 +320,23 @@ void fcu_decision_switch(const fcu_verify_counts *v, const double th_skip[4], co
 /* getCurrentState (tools_YS.cpp:1237-1242) for picture `poc` with g_iP = period, g_iT = n_training, g_iV = n_verifying
  * (reference defaults 60 / 2 / 1, tools_YS.cpp:41-43) */
 int  fcu_frame_state(int poc, int period, int n_training, int n_verifying);
-/* In-loop deblocking of a completely decided all-intra picture, in place on its reconstruction planes:
+/* In-loop deblocking of a completely decided I or P picture, in place on its reconstruction planes:
  * TComLoopFilter::loopFilterPic (TComLoopFilter.cpp:130-155) as TEncGOP::compressGOP runs it after the last slice of the
- * picture (TEncGOP.cpp:1155-1160), with the encoder's default control -- filter enabled, LFCrossSliceBoundaryFlag 1,
- * LFCrossTileBoundaryFlag 1 (TAppEncCfg.cpp:813-818,848-849) -- and the slice's beta / tc offsets (div 2, -6..6).
+ * picture (TEncGOP.cpp:1155-1160), with the encoder's default control -- filter enabled, LFCrossSliceBoundaryFlag 1
+ * (TAppEncCfg.cpp:813-818,848-849) -- and the slice's beta / tc offsets (div 2, -6..6).  It knows no tiles: for a tile picture
+ * it is the filter of LFCrossTileBoundaryFlag 1 (HM's default); either value of that flag: fcu_deblock_tiles.
  * dev_out is the picture's fcu_ctu_out array (depth, part_size, tr_idx and qp are read).  Two kernels on `hip_stream`;
  * asynchronous unless kernel_ms2 is given, which then receives the durations of the vertical- and horizontal-edge pass. */
 int  fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
                  int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream);
+/* fcu_deblock of a picture cut into n_cols x n_rows uniform tiles (fcu_tile_grid) with LFCrossTileBoundaryFlag = lf_cross_tiles:
+ * 1 filters the tile boundaries like any other CTU boundary (what fcu_deblock does); 0 leaves every edge that lies on a tile
+ * boundary unfiltered, luma and chroma, as the picture border is (TComLoopFilter.cpp:379,401,430-434,609-613,754-758) -- the tiles
+ * can then be filtered independently.  A 1 x 1 grid is fcu_deblock byte for byte.  FCU_ERR_ARG: a grid fcu_tile_grid refuses,
+ * lf_cross_tiles outside {0, 1}, a picture beyond 256 CTUs in either direction, and what fcu_deblock refuses. */
+int  fcu_deblock_tiles(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                       int beta_offset_div2, int tc_offset_div2, int n_cols, int n_rows, int lf_cross_tiles,
+                       float *kernel_ms2, void *hip_stream);
 /* ---- sample adaptive offset --------------------------------------------------------------------------------------
  * SAOOffset / SAOBlkParam of the reference (TypeDef.h:760-800) narrowed to bytes: mode 0 off / 1 new / 2 merge;
  * type: edge class 0..3 or 4 = band offset for a new mode, 0 = left / 1 = above for a merge; band = band position;
@@ -347,6 +359,18 @@ typedef struct {
  * (off_count and kernel_ms4 -- statistics, candidates, decision, offset pass -- are read back).  No CPU fallback. */
 int  fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
              fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream);
+/* fcu_sao of pictures cut into n_cols x n_rows uniform tiles (one grid for the batch: a context has one picture size) with
+ * LFCrossTileBoundaryFlag = lf_cross_tiles.  For either value a merge candidate exists only inside the CTU's tile: left iff the
+ * CTU is not in the first column of its tile, above iff not in its first row (TComPic::getSAOMergeAvailability, TComPic.cpp:
+ * 138-143); decideBlkParams still walks the CTUs in raster order over the picture and carries its contexts across the tile
+ * boundaries.  With lf_cross_tiles 0 a CTU of another tile is also unavailable to the statistics and to the offset pass in all
+ * eight directions (TComPicSym::deriveLoopFilterBoundaryAvailibility, TComPicSym.cpp:378,449-459); with 1 sample availability is
+ * the picture border as in fcu_sao.  A 1 x 1 grid is fcu_sao byte for byte.  FCU_ERR_ARG: a grid fcu_tile_grid refuses,
+ * lf_cross_tiles outside {0, 1}, any params[i].slice_ctus != 0 (tiles with SliceMode 1), a picture beyond 256 CTUs in either
+ * direction, and what fcu_sao refuses. */
+int  fcu_sao_tiles(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int n_cols, int n_rows, int lf_cross_tiles,
+                   const uint8_t *const *dev_org, uint8_t *const *dev_rec, fcu_sao_ctu *dev_coded, int32_t *off_count,
+                   float *kernel_ms4, void *hip_stream);
 /* decidePicParams (:363-395): enabled[comp] = 0 when the picture's temporal layer is > 0 and the share of SAO-off CTUs in
  * layer - 1 exceeded 0.75 (luma) / 0.5 (chroma).  rate = m_saoDisabledRate[3][8], zero-initialised by the caller per sequence. */
 void fcu_sao_enabled(const double rate[3][8], int layer, int32_t enabled[3]);

@@ -15,7 +15,8 @@ slices are decided concurrently.  --wpp keeps one slice per picture and switches
 the CTU rows of a picture are decided concurrently, each row starting from the contexts the row above had after its second CTU
 and waiting for the row above to stay two CTUs ahead.  --tiles CxR keeps one slice per picture and cuts it into C x R uniform
 tiles (HM's NumTileColumnsMinus1 / NumTileRowsMinus1 with TileUniformSpacing) decided concurrently; with --wpp the CTU rows of
-every tile are decided concurrently as well.  The slice mode is echoed on every picture line.
+every tile are decided concurrently as well; --lf-cross-tiles 0 makes the deblocking leave the tile boundaries unfiltered (HM's
+LFCrossTileBoundaryFlag, default 1).  The slice mode is echoed on every picture line.
 """
 import argparse
 import os
@@ -47,12 +48,15 @@ def main():
     ap.add_argument("--wpp", action="store_true", help="WaveFrontSynchro: one slice per picture, its CTU rows decided as chains that wait for the row above")
     ap.add_argument("--slice-rows", type=int, default=None, help="with --wpp: SliceMode 1 with slices of this many whole CTU rows, the rows of every slice decided as chains")
     ap.add_argument("--tiles", default=None, metavar="CxR", help="one slice per picture cut into C x R uniform tiles decided as chains; with --wpp, WaveFrontSynchro inside every tile")
+    ap.add_argument("--lf-cross-tiles", type=int, choices=(0, 1), default=None, help="with --tiles: LFCrossTileBoundaryFlag of the deblocking (default 1: the tile boundaries are filtered)")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
     if args.slice_rows is not None and not args.wpp:
         ap.error("--slice-rows needs --wpp (without WaveFrontSynchro: --slice-ctus / --row-slices)")
     tiles = None
+    if args.lf_cross_tiles is not None and args.tiles is None:
+        ap.error("--lf-cross-tiles needs --tiles")
     if args.tiles is not None:
         try:
             tiles = tuple(int(v) for v in args.tiles.lower().split("x"))
@@ -65,7 +69,7 @@ def main():
     pkg = g.load_package()
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
-    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles,
+    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles,
                               schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
