@@ -225,4 +225,12 @@ FCU_DEV int lf_tile_start(const uint64_t *m, int i)
   return (int)((w >> (i & 63)) & 1u);
 }
 
+/* PSNR of a plane of n 8-bit samples from its sum of squared differences, as TEncGOP::xCalculateAddPSNR prints it
+ * (TEncGOP.cpp:2254-2256): the reference value 255 * 255 * n in double precision, 999.99 for an exact reconstruction */
+inline double report_psnr(uint64_t ssd, uint64_t n)
+{
+  const double ref = 255.0 * 255.0 * (double)n;
+  return ssd ? 10.0 * log10(ref / (double)ssd) : 999.99;
+}
+
 } // namespace fcu

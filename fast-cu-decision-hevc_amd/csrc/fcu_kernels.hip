@@ -19,6 +19,7 @@
 #include "fcu_obf.h"
 #include "fcu_deblock.h"
 #include "fcu_sao.h"
+#include "fcu_report.h"
 
 using namespace fcu;
 
@@ -85,6 +86,8 @@ struct fcu_ctx {
   unsigned *d_hist; size_t hist_cap; int *d_thr; size_t thr_cap;
   /* persistent scratch of fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
   void *d_sao; size_t sao_cap;
+  /* persistent scratch of fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
+  void *d_rep; size_t rep_cap;
   /* WaveFrontSynchro (allocated by the first fcu_wpp_begin): d_wpp_ctl = the words a launch polls (ticket, abort, one progress
    * word per chain), a block of its own from the allocation's start, wpp_ctl_bytes a multiple of 16, zeroed before every launch;
    * d_wpp_sync = one sync slot of WPP_SYNC_BYTES per chain */
@@ -134,6 +137,8 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_SAO_CTU: return (int)sizeof(fcu_sao_ctu);
   case FCU_ABI_SAO_PARAMS: return (int)sizeof(fcu_sao_params);
   case FCU_ABI_PU_TRACE: return (int)sizeof(fcu_pu_trace);
+  case FCU_ABI_PIC_REPORT: return (int)sizeof(fcu_pic_report);
+  case FCU_ABI_CTU_REPORT: return (int)sizeof(fcu_ctu_report);
   default: return -1;
   }
 }
@@ -154,7 +159,7 @@ int fcu_create(const fcu_seq_params *sp, fcu_ctx **out)
   fcu_ctx *c = new fcu_ctx();
   c->sp = *sp; c->n_ctu = ((sp->width + 63) / 64) * ((sp->height + 63) / 64);
   c->ms_acc = 0; c->launches = 0;
-  c->d_chains = nullptr; c->d_scratch = nullptr; c->d_hist = nullptr; c->hist_cap = 0; c->d_thr = nullptr; c->thr_cap = 0; c->d_sao = nullptr; c->sao_cap = 0;
+  c->d_chains = nullptr; c->d_scratch = nullptr; c->d_hist = nullptr; c->hist_cap = 0; c->d_thr = nullptr; c->thr_cap = 0; c->d_sao = nullptr; c->sao_cap = 0; c->d_rep = nullptr; c->rep_cap = 0;
   c->d_wpp_ctl = nullptr; c->wpp_ctl_bytes = 0; c->d_wpp_sync = nullptr;
   struct Guard { fcu_ctx *c; ~Guard() { if (c) { hipFree(c->d_chains); hipFree(c->d_scratch); delete c; } } } guard{ c };   /* frees on every early return */
   HIPCHK(hipMalloc((void **)&c->d_chains, sizeof(Chain) * (size_t)sp->max_chains));
@@ -174,7 +179,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->d_hist); hipFree(c->d_thr); hipFree(c->d_sao);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->d_hist); hipFree(c->d_thr); hipFree(c->d_sao); hipFree(c->d_rep);
   hipFree(c->d_wpp_ctl); hipFree(c->d_wpp_sync);
   delete c;
 }
@@ -900,6 +905,58 @@ void fcu_sao_update_rate(double rate[3][8], int layer, const int32_t off_count[3
 {
   if (layer < 0 || layer >= 8 || num_ctus <= 0) return;
   for (int k = 0; k < 3; k++) rate[k][layer] = (double)off_count[k] / (double)num_ctus;
+}
+
+/* TEncGOP::xCalculateAddPSNR of n_pics pictures: report_ctu + report_pic (fcu_report.h), the records back, PSNR on the host */
+int fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, const uint8_t *const *dev_rec, const fcu_ctu_out *const *dev_out,
+                       fcu_pic_report *host_reports, fcu_ctu_report *dev_ctu, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_picture_report: null context");
+  if (n_pics < 1) return fail(FCU_ERR_ARG, "fcu_picture_report: n_pics must be at least 1");
+  if (!dev_org) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_org is null");
+  if (!dev_rec) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_rec is null");
+  if (!dev_out) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_out is null");
+  if (!host_reports) return fail(FCU_ERR_ARG, "fcu_picture_report: host_reports is null");
+  for (int i = 0; i < 3 * n_pics; i++) {
+    if (!dev_org[i]) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_org[" + std::to_string(i) + "] is null");
+    if (!dev_rec[i]) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_rec[" + std::to_string(i) + "] is null");
+  }
+  for (int i = 0; i < n_pics; i++) if (!dev_out[i]) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_out[" + std::to_string(i) + "] is null");
+  HIPCHK(hipSetDevice(c->sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64, n_ctu = c->n_ctu;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_pics = 0, o_rep = up(o_pics + sizeof(ReportPic) * n_pics), o_ctu = up(o_rep + sizeof(fcu_pic_report) * n_pics),
+               total = dev_ctu ? o_ctu : up(o_ctu + sizeof(fcu_ctu_report) * (size_t)n_ctu * n_pics);
+  if (total > c->rep_cap) {
+    if (c->d_rep) { HIPCHK(hipStreamSynchronize(st)); hipFree(c->d_rep); c->d_rep = nullptr; c->rep_cap = 0; }
+    HIPCHK(hipMalloc(&c->d_rep, total)); c->rep_cap = total;
+  }
+  uint8_t *base = (uint8_t *)c->d_rep;
+  ReportPic *d_pics = (ReportPic *)(base + o_pics); fcu_pic_report *d_rep = (fcu_pic_report *)(base + o_rep);
+  fcu_ctu_report *d_ctu = dev_ctu ? dev_ctu : (fcu_ctu_report *)(base + o_ctu);
+  std::vector<ReportPic> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    for (int k = 0; k < 3; k++) { hp[i].org[k] = dev_org[3 * i + k]; hp[i].rec[k] = dev_rec[3 * i + k]; }
+    hp[i].out = dev_out[i];
+  }
+  const bool wide = report_wide_ok(w, hp.data(), n_pics);
+  HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(ReportPic) * n_pics, hipMemcpyHostToDevice, st));
+  hipEvent_t e[3] = { nullptr, nullptr, nullptr };
+  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
+  if (kernel_ms2) { for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
+  if (wide) hipLaunchKernelGGL(report_ctu<true>, dim3(n_ctu, n_pics), dim3(REP_THREADS), 0, st, d_pics, d_ctu, w, h, w_ctu, n_ctu);
+  else hipLaunchKernelGGL(report_ctu<false>, dim3(n_ctu, n_pics), dim3(REP_THREADS), 0, st, d_pics, d_ctu, w, h, w_ctu, n_ctu);
+  HIPCHK(hipGetLastError());
+  if (kernel_ms2) HIPCHK(hipEventRecord(e[1], st));
+  hipLaunchKernelGGL(report_pic, dim3(n_pics), dim3(REP_THREADS), 0, st, d_ctu, d_rep, w, h, n_ctu);
+  HIPCHK(hipGetLastError());
+  if (kernel_ms2) HIPCHK(hipEventRecord(e[2], st));
+  HIPCHK(hipMemcpyAsync(host_reports, d_rep, sizeof(fcu_pic_report) * n_pics, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and host_reports are done with */
+  if (kernel_ms2) { hipEventElapsedTime(&kernel_ms2[0], e[0], e[1]); hipEventElapsedTime(&kernel_ms2[1], e[1], e[2]); }
+  for (int i = 0; i < n_pics; i++) for (int k = 0; k < 3; k++) host_reports[i].psnr[k] = report_psnr(host_reports[i].ssd[k], host_reports[i].n_samples[k]);
+  return FCU_OK;
 }
 
 } /* extern "C" */

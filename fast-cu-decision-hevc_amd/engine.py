@@ -76,6 +76,35 @@ class DecisionParams(C.Structure):
                 ("sw_terminate", C.c_uint8 * 4), ("dev_obf", C.c_void_p)]
 
 
+class CtuReport(C.Structure):
+    """fcu_ctu_report: SSD per plane, bits / bins / distortion and the partition counters of one CTU."""
+    _fields_ = [("ssd", C.c_uint32 * 3), ("bits", C.c_uint32), ("bins", C.c_uint32), ("dist", C.c_uint32),
+                ("n_part", C.c_uint16), ("depth_part", C.c_uint16 * 4), ("part_size_part", C.c_uint16 * 8), ("intra_part", C.c_uint16),
+                ("skip_part", C.c_uint16), ("merge_part", C.c_uint16), ("cbf_part", C.c_uint16 * 3), ("pad", C.c_uint16)]
+
+
+class PicReport(C.Structure):
+    """fcu_pic_report: the sums over a picture's CTUs, the sample counts and the PSNR per plane."""
+    _fields_ = [("ssd", C.c_uint64 * 3), ("bits", C.c_uint64), ("bins", C.c_uint64), ("dist", C.c_uint64), ("n_samples", C.c_uint64 * 3),
+                ("n_part", C.c_uint32), ("depth_part", C.c_uint32 * 4), ("part_size_part", C.c_uint32 * 8), ("intra_part", C.c_uint32),
+                ("skip_part", C.c_uint32), ("merge_part", C.c_uint32), ("cbf_part", C.c_uint32 * 3), ("pad", C.c_uint32),
+                ("psnr", C.c_double * 3)]
+
+
+CTU_REPORT_DTYPE = np.dtype([("ssd", np.uint32, (3,)), ("bits", np.uint32), ("bins", np.uint32), ("dist", np.uint32),
+                             ("n_part", np.uint16), ("depth_part", np.uint16, (4,)), ("part_size_part", np.uint16, (8,)), ("intra_part", np.uint16),
+                             ("skip_part", np.uint16), ("merge_part", np.uint16), ("cbf_part", np.uint16, (3,)), ("pad", np.uint16)])   # fcu_ctu_report
+PIC_REPORT_DTYPE = np.dtype([("ssd", np.uint64, (3,)), ("bits", np.uint64), ("bins", np.uint64), ("dist", np.uint64), ("n_samples", np.uint64, (3,)),
+                             ("n_part", np.uint32), ("depth_part", np.uint32, (4,)), ("part_size_part", np.uint32, (8,)), ("intra_part", np.uint32),
+                             ("skip_part", np.uint32), ("merge_part", np.uint32), ("cbf_part", np.uint32, (3,)), ("pad", np.uint32),
+                             ("psnr", np.float64, (3,))])                                                                   # fcu_pic_report
+
+
+def pic_report_to_dict(rec):
+    """one element of a PIC_REPORT_DTYPE array -> dict of numpy scalars and arrays (`pad` dropped)"""
+    return {n: (rec[n].copy() if rec[n].ndim else rec[n]) for n in PIC_REPORT_DTYPE.names if n != "pad"}
+
+
 class VerifyCounts(C.Structure):
     """fcu_verify_counts: g_iVerResult[depth][TP, FP, TN, FN, FPLoss, FNLoss]."""
     _fields_ = [("n", (C.c_double * 6) * 4)]
@@ -88,7 +117,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_sao", "fcu_sao_enabled", "fcu_sao_update_rate", "fcu_ldp_layer", "fcu_chain_set_pu_trace", "fcu_pu_index", "fcu_chain_set_collocated",
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
-           "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles"]
+           "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -177,6 +206,7 @@ def load_lib():
     lib.fcu_tile_chains.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.fcu_tiles_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int, C.c_int] + [C.c_void_p] * 7
     lib.fcu_wpp_begin_tiles.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameParams), C.c_int, C.c_int] + [C.c_void_p] * 7
+    lib.fcu_picture_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     _lib = lib
     return lib
 
@@ -623,6 +653,38 @@ class CuEngine:
         else:
             self._chk(self.lib.fcu_sao(self.h, n, prm, org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao")
         return coded, off, (list(ms) if timed else None)
+
+    # -- TEncGOP::xCalculateAddPSNR
+    def report(self, pictures, ctu=False, timed=False, stream=None):
+        """The picture report of decided (and filtered) pictures, taken on the device (fcu_picture_report).  pictures: list of
+        dicts {org: (Y,U,V) uint8 device tensors, rec: (Y,U,V) uint8 device tensors, out: the picture's fcu_ctu_out array as a
+        uint8 device tensor}; the planes may be views at any byte offset as long as their rows are dense.  Returns one dict
+        per picture: ssd[3], bits, bins, dist, n_samples[3], n_part, depth_part[4], part_size_part[8], intra_part, skip_part,
+        merge_part, cbf_part[3] (integers, counters in 4x4 luma partitions inside the picture) and psnr[3] (float64, HM's
+        expression).  ctu=True: also the per-CTU records, a structured array [n, n_ctu] of CTU_REPORT_DTYPE; timed=True: also
+        the durations (ms) of the two kernels.  The extras follow the list in that order."""
+        torch = self.torch
+        n = len(pictures)
+        org, rec, out = (C.c_void_p * (3 * n))(), (C.c_void_p * (3 * n))(), (C.c_void_p * n)()
+        for i, p in enumerate(pictures):
+            for k in range(3):
+                w, h = self.width >> (1 if k else 0), self.height >> (1 if k else 0)
+                for t in (p["org"][k], p["rec"][k]):
+                    assert t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w) and t.is_contiguous()
+                org[3 * i + k], rec[3 * i + k] = p["org"][k].data_ptr(), p["rec"][k].data_ptr()
+            o = p["out"]
+            assert o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and o.numel() >= self.n_ctu * CTU_OUT_BYTES
+            out[i] = o.data_ptr()
+        reports = np.zeros(max(n, 1), PIC_REPORT_DTYPE)
+        d_ctu = torch.empty((n, self.n_ctu, CTU_REPORT_DTYPE.itemsize), dtype=torch.uint8, device=torch.device("cuda", self.device)) if ctu else None
+        ms = (C.c_float * 2)() if timed else None
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_picture_report(self.h, n, org, rec, out, reports.ctypes.data, d_ctu.data_ptr() if ctu else None, ms, s), "fcu_picture_report")
+        res = [pic_report_to_dict(reports[i]) for i in range(n)]
+        if not ctu and not timed:
+            return res
+        extra = ([d_ctu.cpu().numpy().view(CTU_REPORT_DTYPE).reshape(n, self.n_ctu)] if ctu else []) + ([(ms[0], ms[1])] if timed else [])
+        return (res, *extra)
 
     # -- TEncCu::destroy
     def destroy(self):

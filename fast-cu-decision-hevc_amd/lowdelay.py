@@ -57,7 +57,7 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
@@ -66,7 +66,10 @@ class LowDelayPDecider:
         when C > 1.
         lf_cross_tiles (with tiles only): LFCrossTileBoundaryFlag of the loop filters, 0 or 1 -- whether deblocking filters the
         tile boundaries and SAO reads samples across them (fcu_deblock_tiles / fcu_sao_tiles).  None means 1 for deblocking,
-        HM's default; sao=True together with tiles asks for an explicit choice."""
+        HM's default; sao=True together with tiles asks for an explicit choice.
+        report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
+        statistics) of the final planes, taken on the device in one batched call for all clips."""
+        self.do_report = report
         if tiles is not None:
             if slice_ctus or slice_rows is not None:
                 raise ValueError("LowDelayPDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
@@ -177,6 +180,9 @@ class LowDelayPDecider:
             for s, r in enumerate(res):
                 r["sao"], r["sao_enabled"] = coded[s], pics[s]["enabled"]
                 self.sao_rate[s].update(layer, off[s], eng.n_ctu)
+        if self.do_report:                                   # on the final planes: after the loop filters that are enabled
+            for r, rep in zip(res, eng.report([{"org": eng._keep[r["first"]][0], "rec": r["rec"], "out": r["out"]} for r in res])):
+                r["report"] = rep
         for s, r in enumerate(res):
             self.col[s] = r["out"]                           # stays in HBM: the next picture's collocated motion field
             self.ref[s] = eng.pad_reference(r["rec"])          # reference of the next picture of this clip

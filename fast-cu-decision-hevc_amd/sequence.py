@@ -78,7 +78,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -92,7 +92,10 @@ class SequenceDecider:
         (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  lf_cross_tiles (with tiles
         only): LFCrossTileBoundaryFlag of the deblocking, 0 or 1 (fcu_deblock_tiles); None means 1, HM's default -- deblocking
         crosses the tile boundaries.  Not with slice_ctus / slice_rows.  This driver runs no SAO: sao=True together with
-        tiles is refused whatever lf_cross_tiles says."""
+        tiles is refused whatever lf_cross_tiles says.
+        report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
+        statistics) of the final planes, taken on the device in one batched call for the pictures of a group."""
+        self.do_report = report
         sao = flags.get("sao")
         if tiles is not None:
             if slice_ctus or slice_rows is not None:
@@ -180,6 +183,9 @@ class SequenceDecider:
                 self.schedule.end_picture(p["poc"], p["verify"])
             if self.do_deblock:
                 eng.deblock(p["first"], tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
+        if self.do_report:                                   # on the final planes: after the deblocking when it is enabled
+            for p, rep in zip(pics, eng.report([{"org": eng._keep[p["first"]][0], "rec": p["rec"], "out": p["out"]} for p in pics])):
+                p["report"] = rep
         eng.sync()
         for p in pics:
             p["depth"] = p["out"].view(eng.n_ctu, nb)[:, :256].cpu().numpy().copy()      # fcu_ctu_out.depth leads the struct

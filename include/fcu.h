@@ -38,6 +38,8 @@
  *     (TComPicSym::initTiles; TEncSlice.cpp            tile-scan order), fcu_wpp_begin_tiles (WaveFrontSynchro inside every
  *      1386-1411,1514-1517,1718-1727;                  tile: one chain per CTU row of every tile), fcu_tile_chains
  *      TComDataCU.cpp:422-440,1071-1390)
+ *   TEncGOP::xCalculateAddPSNR                     fcu_picture_report (SSD per plane -> PSNR, bits, bins, distortion and CU
+ *     (TEncGOP.cpp:2195-2290)                        statistics of decided, filtered pictures; per CTU and per picture)
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -377,6 +379,35 @@ void fcu_sao_enabled(const double rate[3][8], int layer, int32_t enabled[3]);
 /* the bookkeeping at the end of decideBlkParams (:895-917) */
 void fcu_sao_update_rate(double rate[3][8], int layer, const int32_t off_count[3], int num_ctus);
 
+/* ---- the picture report: what the encoder prints per picture (TEncGOP::xCalculateAddPSNR, TEncGOP.cpp:2195-2290) and what a user
+ * of the fast decision looks at -- quality, rate, and how the picture was partitioned -- taken where the picture is, in HBM.
+ * The counters are in units of 4x4 luma partitions and count only partitions inside the picture (a partial CTU's entries
+ * outside it are ignored whatever they hold): n_part = partitions inside; depth_part[d] = partitions of CU depth d (a depth above
+ * 3 is counted nowhere); part_size_part[s] = partitions of PartSize s = 2Nx2N, 2NxN, Nx2N, NxN, 2NxnU, 2NxnD, nLx2N, nRx2N (another
+ * value is counted nowhere); intra_part = pred_mode 1; skip_part / merge_part = skip / merge_flag non-zero; cbf_part[c] = bit 0
+ * (the CU level) of cbf of Y, Cb, Cr.  ssd[c] = sum over the plane's samples inside the picture of (org - rec)^2; bits / bins /
+ * dist = total_bits / total_bins / total_dist of the CTU's record, per picture their sums.  Neither structure has implicit padding. */
+typedef struct fcu_ctu_report {
+  uint32_t ssd[3], bits, bins, dist;                       /* ssd <= 4096 * 255^2 per CTU */
+  uint16_t n_part, depth_part[4], part_size_part[8], intra_part, skip_part, merge_part, cbf_part[3], pad;
+} fcu_ctu_report;
+typedef struct fcu_pic_report {
+  uint64_t ssd[3], bits, bins, dist, n_samples[3];         /* n_samples: width x height, and a quarter of it for Cb and Cr */
+  uint32_t n_part, depth_part[4], part_size_part[8], intra_part, skip_part, merge_part, cbf_part[3], pad;
+  double   psnr[3];                                        /* ssd ? 10 log10(255 * 255 * n_samples / ssd) : 999.99 (TEncGOP.cpp:2254-2256), in double precision on the host */
+} fcu_pic_report;
+/* Report of n_pics pictures of this context's size.  dev_org / dev_rec: host arrays of 3 * n_pics device pointers (Y, U, V of
+ * picture 0, then picture 1 ...), as for fcu_sao; any byte alignment (16-byte aligned planes of a width that is a multiple of
+ * 16 take wider loads); dev_out: host array of n_pics device pointers, each picture's fcu_ctu_out array (only the per-partition
+ * arrays in front of the coefficients and the totals at the end are read).  host_reports receives n_pics records.  dev_ctu
+ * (device, [n_pics][fcu_num_ctus], or NULL: a buffer of the context) receives the per-CTU records.  Nothing is modified but the
+ * outputs; no atomics and no buffer that must be cleared: the same input gives the same bytes.  Two kernels on `hip_stream`; the
+ * call returns after they have finished and the reports are on the host; kernel_ms2 (may be NULL) receives their durations.
+ * FCU_ERR_ARG: n_pics < 1, a NULL array, a NULL entry of one, NULL host_reports.  No CPU fallback. */
+int  fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, const uint8_t *const *dev_rec,
+                        const fcu_ctu_out *const *dev_out, fcu_pic_report *host_reports, fcu_ctu_report *dev_ctu,
+                        float *kernel_ms2, void *hip_stream);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -411,7 +442,7 @@ const char *fcu_build_info(void);
 /* sizeof() of the ABI's structures as this library was compiled, by FCU_ABI_* index (-1 for an unknown index): a binding
  * in another language (ctypes, cgo, JNI) checks its own layouts against them before the first call; tests/test_cabi.py does. */
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
-       FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7 };
+       FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus
