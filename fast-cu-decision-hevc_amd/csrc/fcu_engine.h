@@ -211,9 +211,9 @@ __shared__ HotTables g_hot;
 #if defined(FCU_PROFILE_RQT) && !defined(FCU_EMU)     /* lane 0 of the lane-private RDOQ (the luma variant of an inter TU): slots 11..15 */
 #define FCU_RTIC(v) long long v = clock64()
 #define FCU_RTOC(P_, v, idx) do { if (!SER && threadIdx.x == 0) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
-#elif defined(FCU_PROFILE_RDOQ) && !defined(FCU_EMU)
+#elif defined(FCU_PROFILE_RDOQ) && !defined(FCU_EMU)      /* -DFCU_PROFILE_RDOQ: the serial form; -DFCU_PROFILE_RDOQ=2: lane 0 of the lane-private form (rdoq<0>) */
 #define FCU_RTIC(v) long long v = clock64()
-#define FCU_RTOC(P_, v, idx) do { if (SER) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
+#define FCU_RTOC(P_, v, idx) do { if ((FCU_PROFILE_RDOQ + 0) == 2 ? (!SER && threadIdx.x == 0) : SER) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
 #else
 #define FCU_RTIC(v) do { } while (0)
 #define FCU_RTOC(P_, v, idx) do { } while (0)
@@ -382,14 +382,17 @@ struct Shared {
    * [CAB_LUMA] the coder after the walk of the luma encoding est_intra_pred_luma chose for a 2Nx2N CU */
   Cabac cab[1 + (MAXDEPTH + 1) + MAXLC + 1];
   uint8_t ref5[5][68]; int dc5[5]; uint32_t cm_dist[5];     /* chroma: per-mode reference samples (N <= 16) */
-  /* Three tenants that are never live together (8 KB of LDS per chain = 20 chains per CU, five waves per SIMD):
+  /* Four tenants that are never live together (the union is 1 280 B, the size of rq_grp; 1 040 B before that one came;
+   * 8 688 B of LDS per chain in all = 16 chains per CU, four waves per SIMD):
    *  - reference samples of the block being predicted (+ the availability flags that build them): dead once the
    *    predictions of the batch are in the candidate pools, i.e. before any quantisation;
    *  - the records of the coefficient group in flight in the serial RDOQ;
+   *  - per lane the level_double values of the coefficient group a lane-private RDOQ is walking;
    *  - the |level| lists of the lane-private bit counters. */
   union {
     int16_t lane_abs[MAXLC][32];                    /* per lane: |level| list of the coefficient group being coded [0..15], the group's levels [16..31] */
     RdoqRec rq_rec[16];                             /* serial RDOQ: records of the coefficient group in flight */
+    int32_t rq_grp[16][MAXVC];                      /* lane-private RDOQ: the group being walked, position-major (a read by all lanes is conflict-free) */
     struct {
       int32_t colsum[128];                          /* availability flags of build_ref / chroma_leaf_refs5 */
       union {                                       /* luma reference samples / scratch copy of the chroma sets */
@@ -625,6 +628,20 @@ FCU_DEV int coef_remain_bins(uint32_t symbol, uint32_t rparam)             /* by
   while (code >= (1 << length)) code -= 1 << (length++);
   return (int)(3 + length + 1 - rparam) + (int)length;
 }
+#ifdef FCU_EMU
+/* test bookkeeping of the emulator (tests/test_walk_prefetch_emu.py, tests/emu/walk_asan_driver.cpp): how often the lane-private
+ * walks met their edge cases, and the bounds of the pool rdoq<0> loads from (set by compress_ctu): every address its group loads
+ * form is checked against them, because the pools are members of one Scratch block and no sanitizer sees one run into the next */
+enum { WALK_RDOQ_CALLS, WALK_RDOQ_TOP_IS_GROUP0, WALK_RDOQ_AHEAD_GROUPS, WALK_RDOQ_ONLY_GROUP0, WALK_RDOQ_ONLY_LAST_GROUP, WALK_RDOQ_ALL_ZERO,
+       WALK_BITS_CALLS, WALK_BITS_ONE_EMPTY_RUN_BETWEEN, WALK_BITS_SECOND_ROUND, WALK_N };
+extern "C" { __attribute__((weak)) unsigned long long fcu_emu_walk_cnt[WALK_N]; }
+static const int32_t *g_emu_lscan_lo = nullptr, *g_emu_lscan_hi = nullptr;
+#define FCU_WALK_COUNT(i, n) (fcu_emu_walk_cnt[i] += (unsigned long long)(n))
+#define FCU_CHECK_LSCAN(p) FCU_CHECK((const int32_t *)(p) >= g_emu_lscan_lo && (const int32_t *)(p) < g_emu_lscan_hi)
+#else
+#define FCU_WALK_COUNT(i, n) do { } while (0)
+#define FCU_CHECK_LSCAN(p) do { } while (0)
+#endif
 /* TEncSbac::codeCoeffNxN (+codeTransformSkipFlags, codeLastSignificantXY), TEncSbac.cpp:997-1535.
  * Inside the engine the levels of a TU are kept in SCAN ORDER (coef[sp * st] = level at scan position sp;
  * st = 1 in CU objects, st = number of slots in an interleaved candidate batch), so the coder walks memory
@@ -663,6 +680,14 @@ FCU_DEV FCU_INLINE void code_coeff_body(int c, const int16_t *coef, int st, int 
     }
     if (last < 0) return;
   }
+  FCU_WALK_COUNT(WALK_BITS_CALLS, 1);
+#ifdef FCU_EMU
+  if (log2 == 5) {                                            /* test bookkeeping: one empty 128-byte run (four groups) between two non-empty ones */
+    int e[16];
+    for (int q = 0; q < 16; q++) { e[q] = 1; for (int k = 0; k < 64; k++) if (q * 64 + k <= last && coef[(q * 64 + k) * st]) e[q] = 0; }
+    for (int q = 1; q < (last >> 6); q++) FCU_WALK_COUNT(WALK_BITS_ONE_EMPTY_RUN_BETWEEN, e[q] && !e[q - 1] && !e[q + 1]);
+  }
+#endif
   /* bit/bin totals are kept in registers and added to the coder once at the end (sums commute) */
   uint64_t fr = 0; uint32_t nb = 0;
 #define FCU_BIN(bin_, ctx_) do { const int cx_ = (ctx_); const uint32_t e_ = g_hot.bin[g_S.cab[c].ctx[cx_] * 2 + (bin_)]; nb++; fr += (uint64_t)(e_ >> 8); g_S.cab[c].ctx[cx_] = (uint8_t)e_; } while (0)
@@ -1038,13 +1063,14 @@ FCU_DEV FCU_INLINE RdoqOut rdoq_finish(CB cb, const Params &P, const FCU_HBM int
 
 
 template <int SER, int EST>
-FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int st, int topNZ, int log2, int comp, int scanType, int cbfCtx, const Params &P_, RdoqRec *rec, double *costCGSig)
+/* slot (SER = 0): the caller's lane, < MAXVC: the column of g_S.rq_grp this walk stages its coefficient group in */
+FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int st, int topNZ, int log2, int comp, int scanType, int cbfCtx, const Params &P_, RdoqRec *rec, double *costCGSig, int slot = 0)
 {
   const Params &P = *FCU_UNI(&P_);
   st = FCU_UNI(st); log2 = FCU_UNI(log2); comp = FCU_UNI(comp); cbfCtx = FCU_UNI(cbfCtx);
   if (SER) { c = FCU_UNI(c); src = FCU_UNI(src); dst = FCU_UNI(dst); topNZ = FCU_UNI(topNZ); scanType = FCU_UNI(scanType); rec = FCU_UNI(rec); costCGSig = FCU_UNI(costCGSig); }
   FCU_RTIC(rt_);
-  if (topNZ < 0) { RdoqOut z = { 0, -1 }; return z; }            /* every level is 0: the reference leaves with uiAbsSum 0 (:2330) */
+  if (topNZ < 0) { FCU_WALK_COUNT(WALK_RDOQ_ALL_ZERO, !SER); RdoqOut z = { 0, -1 }; return z; }            /* every level is 0: the reference leaves with uiAbsSum 0 (:2330) */
   const FCU_HBM int32_t *srcg = (const FCU_HBM int32_t *)src; FCU_HBM int16_t *dstg = (FCU_HBM int16_t *)dst;
   FCU_HBM RdoqRec *recg = (FCU_HBM RdoqRec *)rec; FCU_HBM double *cgg = (FCU_HBM double *)costCGSig;
   auto cb = [&](int ctx, int bin) -> int { return EST ? (int)FCU_EST[ctx * 2 + bin] : ctx_bits(c, ctx, bin); };
@@ -1078,8 +1104,32 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
   }
   baseCost = blockUncodedCost;
   FCU_RTOC(P, rt_, 11);                                       /* set-up + uncoded tail */
-  int32_t ahead = srcg[(cgTop * 16 + 15) * st];
+  /* SER = 0: a group is fetched as a group: sixteen loads issued together, one round trip per group where the load one
+   * coefficient ahead paid a partly exposed round trip on every short iteration.  The loads of group cg - 1 are written at the
+   * top of the walk of group cg, but that is NOT an overlap with the walk in the compiled kernel: the flat load of
+   * scanCG[cgScanPos] follows them, loads retire in order, and its s_waitcnt vmcnt(0) waits for all sixteen.  (Reading scanCG
+   * one group ahead through typed pointers does remove that wait, but a table read still stalls at the group top for TUs above
+   * 8x8 and the private segment grows by 250 B: not shipped)  The values are parked in the lane's column of
+   * g_S.rq_grp, which the coefficient loop indexes (a register array indexed by the position would live in scratch memory).
+   * SER = 1 keeps the load one coefficient ahead. */
+  constexpr bool GRP = !SER;
+  int32_t ahead = 0, nxt[16];
+  if (GRP) {
+    FCU_CHECK(slot >= 0 && slot < MAXVC);
+#pragma unroll
+    for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[(cgTop * 16 + k) * st]); nxt[k] = srcg[(cgTop * 16 + k) * st]; }
+    FCU_WALK_COUNT(WALK_RDOQ_CALLS, 1); FCU_WALK_COUNT(WALK_RDOQ_TOP_IS_GROUP0, cgTop == 0);
+  } else ahead = srcg[(cgTop * 16 + 15) * st];
   for (int cgScanPos = cgTop; cgScanPos >= 0; cgScanPos--) {
+    if (GRP) {
+#pragma unroll
+      for (int k = 0; k < 16; k++) g_S.rq_grp[k][slot] = nxt[k];
+      if (cgScanPos > 0) {                                    /* group 0 has no successor: no address below scan position 0 is formed */
+        FCU_WALK_COUNT(WALK_RDOQ_AHEAD_GROUPS, 1);
+#pragma unroll
+        for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[((cgScanPos - 1) * 16 + k) * st]); nxt[k] = srcg[((cgScanPos - 1) * 16 + k) * st]; }
+      }
+    }
     const int cgBlk = scanCG[cgScanPos], cgy = cgBlk / wg, cgx = cgBlk - cgy * wg;
     double rdSigCost = 0, rdSigCost0 = 0, rdCodedLevelandDist = 0, rdUncodedDist = 0; int nnzBeforePos0 = 0;
     const int pattern = pattern_sig_ctx(cgflag, cgx, cgy, wg);
@@ -1095,8 +1145,12 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
     const uint32_t cntBits = g_hot.cnt_bits[pattern];
     for (int posInCG = 15; posInCG >= 0; posInCG--) {
       const int scanPos = cgScanPos * 16 + posInCG;
-      const int32_t levelDouble = iabs(ahead);
-      if (scanPos > 0) ahead = srcg[(scanPos - 1) * st];      /* one ahead: its latency overlaps this coefficient's work */
+      int32_t levelDouble;
+      if (GRP) levelDouble = iabs(g_S.rq_grp[posInCG][slot]);
+      else {
+        levelDouble = iabs(ahead);
+        if (scanPos > 0) ahead = srcg[(scanPos - 1) * st];    /* one ahead: its latency overlaps this coefficient's work */
+      }
       uint32_t maxAbsLevel = (uint32_t)((levelDouble + ((int32_t)1 << (qbits - 1))) >> qbits);
       if (maxAbsLevel > 32767u) maxAbsLevel = 32767u;
       const double err = (double)levelDouble;
@@ -1208,6 +1262,14 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
   }
   FCU_RTOC(P, rt_, 12);                                       /* main loop */
   if (lastScanPos < 0) { RdoqOut z = { 0, -1 }; return z; }
+#ifdef FCU_EMU
+  FCU_WALK_COUNT(WALK_RDOQ_ONLY_GROUP0, GRP && lastScanPos < 16);
+  if (GRP && n2 > 16 && lastScanPos >= n2 - 16) {             /* test bookkeeping: every level below the last group is 0 */
+    int other = 0;
+    for (int sp = 0; sp < n2 - 16; sp++) other |= dstg[sp * st];
+    FCU_WALK_COUNT(WALK_RDOQ_ONLY_LAST_GROUP, !other);
+  }
+#endif
   return rdoq_finish<SER>(cb, P, srcg, dstg, recg, cgg, st, log2, ch, scanType, cbfCtx, scan, scanCG, cgflag, cgLastScanPos, lastScanPos, baseCost, blockUncodedCost, lambda);
 }
 
@@ -2620,7 +2682,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
       const int mode = g_S.rd_mode[(lane >> tss)];
       RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
       const int cbfCtx = CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0);
-      const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq) ? rdoq<0, 1>(CAB_CUR0 + d, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, coef_scan_idx(mode, log2, 0), cbfCtx, P, rrec, rcg)
+      const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq) ? rdoq<0, 1>(CAB_CUR0 + d, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, coef_scan_idx(mode, log2, 0), cbfCtx, P, rrec, rcg, lane)
                                                             : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, P);
       g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last;
       g_S.vc_dist[lane] = 0;
@@ -2670,6 +2732,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
 #if defined(FCU_EMU) && defined(FCU_EMU_TRACE_ROUNDS)
     if (vbase) fprintf(stderr, "second bit-count round: %d variants\n", nvc);
 #endif
+    FCU_WALK_COUNT(WALK_BITS_SECOND_ROUND, vbase != 0);
     FCU_FOR_LANES {
       const int vc = vbase + lane;
       if (lane < MAXLC && vc < nvc) {
@@ -2776,7 +2839,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_64(CuObj *cu, uint32_t root_k)
       if (lane < nc) {
         RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
         const RdoqOut o = P.rdoq ? rdoq<0, 0>(CAB_LANE0 + lane, G->p_lscan + lane, G->p_qscan + lane, nc, g_S.vc_last[lane], log2, 0,
-                                              coef_scan_idx(g_S.rd_mode[lane], log2, 0), CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0), P, rrec, rcg)
+                                              coef_scan_idx(g_S.rd_mode[lane], log2, 0), CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0), P, rrec, rcg, lane)
                                  : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nc, g_S.vc_last[lane], log2, 0, P);
         g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last; g_S.vc_dist[lane] = 0;
       }
@@ -3078,7 +3141,7 @@ FCU_DEV FCU_NOINLINE void chroma_leaf_trials(CuObj *cu, uint32_t tu_k)
         const int mode = g_S.c_modes[m] == DM_CHROMA ? lumaDir : g_S.c_modes[m];
         RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
         const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq)
-          ? rdoq<0, 0>(CAB_LANE0 + m, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1 /* Cb and Cr share every parameter the call reads; the argument is wave-uniform */, coef_scan_idx(mode, log2, comp), CTX_CBF_CHROMA + trDepth, P, rrec, rcg)
+          ? rdoq<0, 0>(CAB_LANE0 + m, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1 /* Cb and Cr share every parameter the call reads; the argument is wave-uniform */, coef_scan_idx(mode, log2, comp), CTX_CBF_CHROMA + trDepth, P, rrec, rcg, lane)
           : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1, P);
         g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last;
         g_S.vc_dist[lane] = 0;
@@ -3628,6 +3691,9 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int pos)
 {
   C = FCU_UNI(C); G = FCU_UNI(G); pos = FCU_UNI(pos);
   Env E; E.C = C; E.G = G;
+#ifdef FCU_EMU
+  g_emu_lscan_lo = G->p_lscan; g_emu_lscan_hi = G->p_lscan + POOL;
+#endif
   FCU_TIC(t10_);
   const Params &P = C->p;
   const int tileW = FCU_UNI(C->tile_w), tileX0 = FCU_UNI(C->tile_x0), tileY0 = FCU_UNI(C->tile_y0);
