@@ -13,6 +13,8 @@ import os
 
 import numpy as np
 
+from .layout import PictureLayout
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NPART = 256
 
@@ -289,6 +291,7 @@ class CuEngine:
     init_chain()    <- TEncCu::init + TEncSlice::setUpLambda : binds planes, QP, lambda
     compress_ctu()  <- TEncCu::compressCtu + encodeCtu : one CTU of one chain, result to host
     compress_chains(): the batched form, many chains x k CTUs per launch
+    init_picture() / compress_pictures(): one picture as the chains of a PictureLayout (slices, WPP rows, tiles)
     destroy()       <- TEncCu::destroy
     """
 
@@ -318,6 +321,28 @@ class CuEngine:
             raise FcuError(f"{what} failed ({r}): {self.lib.fcu_last_error().decode()}")
 
     # -- TEncCu::init + slice parameters
+    def _open(self, org, qp, rec, out, params, flags, who):
+        """what every binder starts with: the planes on the device, rec / out allocated when None, the frame parameters from
+        `params` or the I-slice defaults for `qp`, with `flags` applied.  Returns planes, rec, out, fp."""
+        torch = self.torch
+        dev = torch.device("cuda", self.device)
+        planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
+        if rec is None:
+            rec = [torch.zeros_like(p) for p in planes]
+        if out is None:
+            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
+        fp = FrameParams()
+        if params is not None:
+            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
+        else:
+            self.lib.fcu_default_frame_params(C.byref(fp), qp)
+        known = {n for n, _ in FrameParams._fields_}
+        for k, v in flags.items():
+            if k not in known:                                  # a misspelt tool flag must not be dropped silently
+                raise TypeError(f"{who}: unknown frame parameter {k!r} (fcu_frame_params has {sorted(known)})")
+            setattr(fp, k, v)
+        return planes, rec, out, fp
+
     def init_chain(self, chain, org, qp, slice_ctus=0, rec=None, out=None, ref=None, params=None, col=None,
                    refs=None, ref_pocs=None, poc=None, col_ref_pocs=None, **flags):
         """org: (Y,U,V) uint8 torch tensors on this device (or numpy arrays, uploaded once).
@@ -328,32 +353,64 @@ class CuEngine:
         with their POCs and this picture's POC; col_ref_pocs: the POCs the list 0 of refs[0] (the collocated picture) named."""
         if refs is not None:
             assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
-        torch = self.torch
-        dev = torch.device("cuda", self.device)
-        planes = []
-        for a in org:
-            t = torch.as_tensor(a) if not torch.is_tensor(a) else a
-            planes.append(t.to(device=dev, dtype=torch.uint8).contiguous())
-        if rec is None:
-            rec = [torch.zeros_like(p) for p in planes]
-        if out is None:
-            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
-        fp = FrameParams()
-        if params is not None:
-            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
-        else:
-            self.lib.fcu_default_frame_params(C.byref(fp), qp)
+        planes, rec, out, fp = self._open(org, qp, rec, out, params, flags, "init_chain")
         fp.slice_ctus = slice_ctus
-        known = {n for n, _ in FrameParams._fields_}
-        for k, v in flags.items():
-            if k not in known:                                  # a misspelt tool flag must not be dropped silently
-                raise TypeError(f"init_chain: unknown frame parameter {k!r} (fcu_frame_params has {sorted(known)})")
-            setattr(fp, k, v)
         self._chk(self.lib.fcu_chain_begin(self.h, chain, C.byref(fp), *[p.data_ptr() for p in planes],
                                            *[p.data_ptr() for p in rec], out.data_ptr()), "fcu_chain_begin")
         self._keep[chain] = (planes, rec, out)
         self._bind_refs(chain, ref, refs, ref_pocs, poc, col_ref_pocs, col)
         return rec, out
+
+    def init_picture(self, first_chain, org, qp, layout, rec=None, out=None, params=None, ref=None, refs=None, ref_pocs=None, poc=None,
+                     col_ref_pocs=None, col=None, search_state=None, **flags):
+        """One picture as the chains [first_chain, first_chain + layout.chains) of a PictureLayout; they share the picture's
+        planes and fcu_ctu_out array.  org / rec / out / params / flags as init_chain takes them (I or P by params.slice_type).
+          slices         one chain per slice, in order (fcu_chain_begin + fcu_chain_set_range; one slice: a single chain bound
+                         with slice_ctus 0); compress_chains advances them;
+          wpp            one chain per CTU row, top to bottom (fcu_wpp_begin, fcu_wpp_begin_p for a P slice; with slice_rows
+                         fcu_wpp_begin_slices: the first row of every slice waits for nothing and starts from a zero search
+                         state); decided by compress_wpp;
+          tiles          one chain per tile in tile-scan order, each raster-in-tile (fcu_tiles_begin); with wpp one chain per CTU
+                         row of every tile, rows top to bottom (fcu_wpp_begin_tiles).  Every tile starts from a zero search state.
+        A P picture takes ref or refs / ref_pocs / poc / col_ref_pocs and col (init_chain) on every chain, and search_state
+        (set_search_state: what the previous picture left; zero when None) on the first chain.  set_decision rewrites the search
+        state: a caller that sets decision states passes search_state=None and calls set_search_state(first_chain, ...) after its
+        set_decision calls.  compress_pictures launches what was bound.  Returns (n_chains, rec, out)."""
+        if refs is not None:
+            assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
+        assert layout.n_ctu == self.n_ctu
+        planes, rec, out, fp = self._open(org, qp, rec, out, params, flags, "init_picture")
+        p_slice = fp.slice_type == SLICE_P
+        ptrs = [p.data_ptr() for p in planes] + [p.data_ptr() for p in rec] + [out.data_ptr()]
+        if layout.tiles is not None:
+            name, args = "fcu_wpp_begin_tiles" if layout.wpp else "fcu_tiles_begin", [int(v) for v in layout.tiles]
+        elif layout.slice_rows is not None:
+            name, args = "fcu_wpp_begin_slices", [int(layout.slice_rows)]
+        elif layout.wpp:
+            name, args = "fcu_wpp_begin_p" if p_slice else "fcu_wpp_begin", []
+        else:
+            name, sl = None, layout.bind_slice_ctus
+            fp.slice_ctus = sl
+            for k in range(layout.chains):
+                self._chk(self.lib.fcu_chain_begin(self.h, first_chain + k, C.byref(fp), *ptrs), "fcu_chain_begin")
+                if sl:
+                    self.set_range(first_chain + k, k * sl, min(sl, self.n_ctu - k * sl))
+        if name:
+            self._chk(getattr(self.lib, name)(self.h, first_chain, C.byref(fp), *args, *ptrs), name)
+        for k in range(layout.chains):
+            self._keep[first_chain + k] = (planes, rec, out)
+            if p_slice:
+                self._bind_refs(first_chain + k, ref, refs, ref_pocs, poc, col_ref_pocs, col)
+        if p_slice and search_state is not None:
+            self.set_search_state(first_chain, search_state)
+        return layout.chains, rec, out
+
+    def compress_pictures(self, first, n_pictures, layout, stream=None):
+        """decides n_pictures pictures bound by init_picture with this layout at consecutive chains from `first`, to their end"""
+        if layout.uses_wpp_launch:
+            self.compress_wpp(first, n_pictures * layout.chains, stream)
+        else:
+            self.compress_chains(first, n_pictures * layout.chains, layout.launch_ctus, stream)
 
     def _bind_refs(self, chain, ref=None, refs=None, ref_pocs=None, poc=None, col_ref_pocs=None, col=None):
         """reference pictures and collocated field of a bound chain (init_chain's arguments of the same names)"""
@@ -398,64 +455,17 @@ class CuEngine:
         return out
 
     def init_slice_chains(self, first_chain, org, qp, slice_ctus, **flags):
-        """One frame as ceil(n_ctu / slice_ctus) chains, one per slice (SliceMode 1): they share the frame's
-        source / reconstruction planes and fcu_ctu_out array.  Returns (n_slices, rec, out)."""
-        n_sl = (self.n_ctu + slice_ctus - 1) // slice_ctus
-        rec, out = self.init_chain(first_chain, org, qp, slice_ctus=slice_ctus, **flags)
-        planes = self._keep[first_chain][0]
-        for k in range(n_sl):
-            if k:
-                self.init_chain(first_chain + k, planes, qp, slice_ctus=slice_ctus, rec=rec, out=out, **flags)
-            first = k * slice_ctus
-            self.set_range(first_chain + k, first, min(slice_ctus, self.n_ctu - first))
-        return n_sl, rec, out
+        """One frame as ceil(n_ctu / slice_ctus) chains, one per slice (SliceMode 1): init_picture with that layout;
+        flags may name its other arguments.  Returns (n_slices, rec, out)."""
+        return self.init_picture(first_chain, org, qp, PictureLayout(self.width, self.height, slice_ctus=slice_ctus, who="init_slice_chains"), **flags)
 
     def init_wpp_picture(self, first_chain, org, qp, rec=None, out=None, params=None, ref=None, refs=None, ref_pocs=None, poc=None,
                          col_ref_pocs=None, col=None, search_state=None, slice_rows=None, **flags):
-        """One picture, one slice, WaveFrontSynchro on: chains [first_chain, first_chain + n_rows) become its CTU rows, top to
-        bottom; they share the picture's planes and fcu_ctu_out array.  params / flags: the frame parameters as init_chain takes
-        them (I-slice defaults for `qp` without params).  An I slice binds with fcu_wpp_begin; a P slice (params.slice_type P)
-        with fcu_wpp_begin_p, and then takes ref or refs / ref_pocs / poc / col_ref_pocs and col (init_chain) on every row and
-        search_state (set_search_state: what the previous picture left; zero when None) on row 0.  set_decision rewrites the
-        search state: a caller that sets decision states passes search_state=None and calls set_search_state(first_chain, ...)
-        after its set_decision calls.
-        slice_rows: WaveFrontSynchro with SliceMode 1 -- the picture is cut into independent slices of slice_rows whole CTU
-        rows (fcu_wpp_begin_slices, I or P by params.slice_type): the first row of every slice waits for nothing and starts from
-        a zero search state; search_state, if given, goes to row 0 (the first slice) only.  Returns (n_rows, rec, out)."""
-        if refs is not None:
-            assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
-        torch = self.torch
-        dev = torch.device("cuda", self.device)
-        planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
-        if rec is None:
-            rec = [torch.zeros_like(p) for p in planes]
-        if out is None:
-            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
-        fp = FrameParams()
-        if params is not None:
-            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
-        else:
-            self.lib.fcu_default_frame_params(C.byref(fp), qp)
-        known = {n for n, _ in FrameParams._fields_}
-        for k, v in flags.items():
-            if k not in known:
-                raise TypeError(f"init_wpp_picture: unknown frame parameter {k!r}")
-            setattr(fp, k, v)
-        p_slice = fp.slice_type == SLICE_P
-        ptrs = [p.data_ptr() for p in planes] + [p.data_ptr() for p in rec] + [out.data_ptr()]
-        if slice_rows is not None:
-            self._chk(self.lib.fcu_wpp_begin_slices(self.h, first_chain, C.byref(fp), int(slice_rows), *ptrs), "fcu_wpp_begin_slices")
-        else:
-            begin, name = (self.lib.fcu_wpp_begin_p, "fcu_wpp_begin_p") if p_slice else (self.lib.fcu_wpp_begin, "fcu_wpp_begin")
-            self._chk(begin(self.h, first_chain, C.byref(fp), *ptrs), name)
-        n_rows = self.lib.fcu_wpp_rows(self.h)
-        for r in range(n_rows):
-            self._keep[first_chain + r] = (planes, rec, out)
-            if p_slice:
-                self._bind_refs(first_chain + r, ref, refs, ref_pocs, poc, col_ref_pocs, col)
-        if p_slice and search_state is not None:
-            self.set_search_state(first_chain, search_state)
-        return n_rows, rec, out
+        """One picture with WaveFrontSynchro on, its CTU rows as chains: init_picture with the layout wpp=True, slice_rows
+        (None: one slice; N: independent slices of N whole CTU rows).  Returns (n_rows, rec, out)."""
+        lo = PictureLayout(self.width, self.height, wpp=True, slice_rows=slice_rows, who="init_wpp_picture")
+        return self.init_picture(first_chain, org, qp, lo, rec=rec, out=out, params=params, ref=ref, refs=refs, ref_pocs=ref_pocs, poc=poc,
+                                 col_ref_pocs=col_ref_pocs, col=col, search_state=search_state, **flags)
 
     def tile_chains(self, n_cols, n_rows, wpp=False):
         """chains init_tile_picture binds for this grid (fcu_tile_chains); -1: no such grid"""
@@ -463,41 +473,11 @@ class CuEngine:
 
     def init_tile_picture(self, first_chain, org, qp, n_cols, n_rows, wpp=False, rec=None, out=None, params=None, ref=None, refs=None,
                           ref_pocs=None, poc=None, col_ref_pocs=None, col=None, **flags):
-        """One picture, one slice, cut into n_cols x n_rows uniform tiles (HM's TileUniformSpacing).  wpp=False: chains
-        [first_chain, first_chain + n_cols * n_rows) become its tiles in tile-scan order (fcu_tiles_begin) and compress_chains
-        advances them, each raster-in-tile.  wpp=True: WaveFrontSynchro inside every tile -- one chain per CTU row of every tile,
-        tiles in tile-scan order, rows top to bottom (fcu_wpp_begin_tiles), decided by compress_wpp.  The chains share the
-        picture's planes and fcu_ctu_out array.  params / flags: the frame parameters as init_chain takes them (I or P by
-        params.slice_type); a P picture takes ref or refs / ref_pocs / poc / col_ref_pocs and col on every chain.  Every tile
-        starts from a zero search state.  Returns (n_chains, rec, out)."""
-        if refs is not None:
-            assert ref is None and 1 <= len(refs) <= MAX_REF and len(ref_pocs) == len(refs) and poc is not None
-        torch = self.torch
-        dev = torch.device("cuda", self.device)
-        planes = [(torch.as_tensor(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.uint8).contiguous() for a in org]
-        if rec is None:
-            rec = [torch.zeros_like(p) for p in planes]
-        if out is None:
-            out = torch.zeros(self.n_ctu * CTU_OUT_BYTES, dtype=torch.uint8, device=dev)
-        fp = FrameParams()
-        if params is not None:
-            C.memmove(C.byref(fp), C.byref(params), C.sizeof(FrameParams))
-        else:
-            self.lib.fcu_default_frame_params(C.byref(fp), qp)
-        known = {n for n, _ in FrameParams._fields_}
-        for k, v in flags.items():
-            if k not in known:
-                raise TypeError(f"init_tile_picture: unknown frame parameter {k!r}")
-            setattr(fp, k, v)
-        ptrs = [p.data_ptr() for p in planes] + [p.data_ptr() for p in rec] + [out.data_ptr()]
-        begin, name = (self.lib.fcu_wpp_begin_tiles, "fcu_wpp_begin_tiles") if wpp else (self.lib.fcu_tiles_begin, "fcu_tiles_begin")
-        self._chk(begin(self.h, first_chain, C.byref(fp), int(n_cols), int(n_rows), *ptrs), name)
-        n = self.tile_chains(n_cols, n_rows, wpp)
-        for k in range(n):
-            self._keep[first_chain + k] = (planes, rec, out)
-            if fp.slice_type == SLICE_P:
-                self._bind_refs(first_chain + k, ref, refs, ref_pocs, poc, col_ref_pocs, col)
-        return n, rec, out
+        """One picture, one slice, cut into n_cols x n_rows uniform tiles (HM's TileUniformSpacing), with wpp WaveFrontSynchro
+        inside every tile: init_picture with the layout tiles=(n_cols, n_rows), wpp.  Returns (n_chains, rec, out)."""
+        lo = PictureLayout(self.width, self.height, wpp=wpp, tiles=(n_cols, n_rows), who="init_tile_picture")
+        return self.init_picture(first_chain, org, qp, lo, rec=rec, out=out, params=params, ref=ref, refs=refs, ref_pocs=ref_pocs, poc=poc,
+                                 col_ref_pocs=col_ref_pocs, col=col, **flags)
 
     def compress_wpp(self, first, n, stream=None):
         """decides the WPP row chains [first, first + n) (whole pictures) to the end in one launch; returns once it has finished"""
@@ -545,6 +525,10 @@ class CuEngine:
 
     def rec_planes(self, chain):
         return [p.cpu().numpy() for p in self._keep[chain][1]]
+
+    def org_planes(self, chain):
+        """the source planes the chain was bound with, as uploaded: (Y, U, V) uint8 device tensors"""
+        return self._keep[chain][0]
 
     def ctu_out(self, chain, ctu_rs_addr):
         buf = self._keep[chain][2][ctu_rs_addr * CTU_OUT_BYTES:(ctu_rs_addr + 1) * CTU_OUT_BYTES].cpu().numpy()
@@ -601,12 +585,14 @@ class CuEngine:
         return trace.cpu().numpy().view(PU_TRACE_DTYPE).reshape(self.n_ctu, PUS_PER_CTU)
 
     # -- TComLoopFilter::loopFilterPic
-    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1):
+    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1, layout=None):
         """Deblocks, in place, the reconstruction planes bound to `chain` (all slice chains of a picture share them)
         once every CTU of the picture has been decided -- or explicit device tensors: `out` = the picture's
         fcu_ctu_out array as uint8, `rec` = (Y, U, V).  tiles=(C, R): the picture's uniform tile grid, filtered with
         LFCrossTileBoundaryFlag = lf_cross_tiles (fcu_deblock_tiles; 0 leaves the tile boundaries unfiltered); without tiles
-        lf_cross_tiles is not looked at.  Returns (ms vertical pass, ms horizontal pass) if timed."""
+        lf_cross_tiles is not looked at; layout: a PictureLayout to take both from.  Returns (ms vertical pass, ms horizontal pass) if timed."""
+        if layout is not None:
+            tiles, lf_cross_tiles = layout.tiles, layout.lf_cross_tiles
         if chain is not None:
             _, rec, out = self._keep[chain]
         assert out.numel() >= self.n_ctu * CTU_OUT_BYTES and rec[0].numel() == self.width * self.height
@@ -621,14 +607,16 @@ class CuEngine:
         return (ms[0], ms[1]) if timed else None
 
     # -- TEncSampleAdaptiveOffset::SAOProcess
-    def sao(self, pictures, timed=False, stream=None, tiles=None, lf_cross_tiles=1):
+    def sao(self, pictures, timed=False, stream=None, tiles=None, lf_cross_tiles=1, layout=None):
         """SAO of completely decided, deblocked pictures, in place on their reconstruction planes.  pictures: list of dicts
         {org: (Y,U,V) device tensors, rec: (Y,U,V) device tensors, qp, lambda_ (the slice's luma lambda), slice_type,
         slice_ctus, enabled (3 ints, default all on), chroma_weight (default: from the QP, chroma QP offset 0)}.
         tiles=(C, R): every picture of the batch is cut into C x R uniform tiles (fcu_sao_tiles): merge candidates stay inside
         the CTU's tile, and with lf_cross_tiles=0 (LFCrossTileBoundaryFlag) so do the samples the statistics and the offset pass
-        read; slice_ctus must then be 0.  Returns (coded uint8 tensor
+        read; slice_ctus must then be 0; layout: a PictureLayout to take both from.  Returns (coded uint8 tensor
         [n, n_ctu, SAO_CTU_BYTES] on the device, off_count int32 array [n, 3], kernel ms x4 or None)."""
+        if layout is not None:
+            tiles, lf_cross_tiles = layout.tiles, layout.lf_cross_tiles
         torch = self.torch
         n = len(pictures)
         dev = torch.device("cuda", self.device)
@@ -693,6 +681,7 @@ class CuEngine:
             self.h = C.c_void_p()
         self._keep = {}
         self._keep_obf = {}
+        self._keep_ref = {}
 
     def __del__(self):
         try:

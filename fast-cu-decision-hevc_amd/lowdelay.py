@@ -36,6 +36,7 @@ from TComSlice::getEncCABACTableIdx (adapter/TEncCuFcu.cpp).
 import numpy as np
 
 from . import engine as _engine
+from .layout import PictureLayout
 
 HM_LDP_RPS = {1: (-1, -5, -9, -13), 2: (-1, -2, -6, -10), 3: (-1, -3, -7, -11), 0: (-1, -4, -8, -12)}     # reference pictures of Frame1..Frame4 in encoder_lowdelay_P_main.cfg
 
@@ -62,45 +63,18 @@ class LowDelayPDecider:
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
         (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles: one chain per CTU row of every
-        tile).  Every tile of every picture starts from a zero search state.  Not with slice_ctus / slice_rows, and not with tmvp
-        when C > 1.
+        tile).  Every tile of every picture starts from a zero search state.  PictureLayout holds the rules of these combinations.
         lf_cross_tiles (with tiles only): LFCrossTileBoundaryFlag of the loop filters, 0 or 1 -- whether deblocking filters the
         tile boundaries and SAO reads samples across them (fcu_deblock_tiles / fcu_sao_tiles).  None means 1 for deblocking,
         HM's default; sao=True together with tiles asks for an explicit choice.
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
         statistics) of the final planes, taken on the device in one batched call for all clips."""
         self.do_report = report
-        if tiles is not None:
-            if slice_ctus or slice_rows is not None:
-                raise ValueError("LowDelayPDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
-            if lf_cross_tiles is not None and lf_cross_tiles not in (0, 1):
-                raise ValueError("LowDelayPDecider: lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1")
-            if sao and lf_cross_tiles is None:
-                raise ValueError("LowDelayPDecider: sao=True together with tiles needs lf_cross_tiles=0 or 1 (LFCrossTileBoundaryFlag: whether SAO and deblocking reach across the tile boundaries)")
-            _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
-            if tmvp and tiles[0] > 1:
-                raise ValueError("LowDelayPDecider: tmvp together with tile columns is not supported (the collocated bottom-right candidate reads across the tile edge)")
-        elif lf_cross_tiles is not None:
-            raise ValueError("LowDelayPDecider: lf_cross_tiles is the loop filters' flag of a picture with tiles and needs tiles=(C, R)")
-        self.tiles = tiles
-        self.lf_cross_tiles = 1 if lf_cross_tiles is None else lf_cross_tiles
-        if wpp and slice_ctus:
-            raise ValueError("LowDelayPDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
-        if slice_rows is not None and not wpp:
-            raise ValueError("LowDelayPDecider: slice_rows cuts a WaveFrontSynchro picture into slices of whole CTU rows and needs wpp=True (without WPP: slice_ctus)")
-        if slice_rows is not None and slice_rows < 1:
-            raise ValueError("LowDelayPDecider: slice_rows must be at least 1")
-        self.wpp, self.slice_rows = wpp, slice_rows
+        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, tmvp=tmvp, who="LowDelayPDecider")
+        self.tiles, self.lf_cross_tiles, self.wpp, self.slice_rows, self.slice_ctus = tiles, lo.lf_cross_tiles, wpp, slice_rows, lo.slice_ctus
+        self.n_slices, self.n_chains, self.sao_slice_ctus = lo.n_slices, lo.chains, lo.sao_slice_ctus
         self.width, self.height, self.base_qp, self.n_clips, self.search_range = width, height, base_qp, n_clips, search_range
-        n_ctu = ((width + 63) // 64) * ((height + 63) // 64)
-        self.slice_ctus = slice_ctus if slice_ctus else n_ctu
-        self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
-        self.sao_slice_ctus = self.slice_ctus if self.n_slices > 1 else 0      # what fcu_sao is told
-        if slice_rows is not None:
-            self.sao_slice_ctus = slice_rows * ((width + 63) // 64)
-        self.n_chains = (height + 63) // 64 if wpp else self.n_slices          # chains per picture: rows (WPP) or slices
-        if tiles is not None:
-            self.n_chains = tiles[0] * ((height + 63) // 64 if wpp else tiles[1])      # fcu_tile_chains
+        self.carry_search_state = lo.wpp and slice_rows is None and tiles is None      # one slice of WPP rows: HM's state goes from picture to picture
         self.search_state = [None] * n_clips             # WPP: m_integerMv2Nx2N after each clip's last picture
         self.eng = _engine.CuEngine(width, height, max_chains=n_clips * self.n_chains, device=device)
         self.do_deblock = deblock
@@ -141,47 +115,28 @@ class LowDelayPDecider:
             kw = dict(ref=ref)
             if ref is not None and self.n_refs > 1:
                 kw = dict(refs=[self.dpb[s][q][0] for q in rl], ref_pocs=rl, poc=poc, col_ref_pocs=self.dpb[s][rl[0]][1])
-            if self.tiles is not None:
-                _, rec, out = eng.init_tile_picture(first, f, fp.qp, *self.tiles, wpp=self.wpp, params=fp, col=col, **kw)
-                res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
-                continue
-            if self.wpp:
-                state = self.search_state[s] if (fp.slice_type == _engine.SLICE_P and self.slice_rows is None) else None
-                _, rec, out = eng.init_wpp_picture(first, f, fp.qp, params=fp, col=col, search_state=state, slice_rows=self.slice_rows, **kw)
-                res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
-                continue
-            rec, out = eng.init_chain(first, f, fp.qp, slice_ctus=self.slice_ctus if self.n_slices > 1 else 0, params=fp, col=col, **kw)
-            planes = eng._keep[first][0]
-            for k in range(self.n_slices):
-                if k:
-                    eng.init_chain(first + k, planes, fp.qp, slice_ctus=self.slice_ctus, rec=rec, out=out, params=fp, col=col, **kw)
-                if self.n_slices > 1:
-                    a = k * self.slice_ctus
-                    eng.set_range(first + k, a, min(self.slice_ctus, eng.n_ctu - a))
+            state = self.search_state[s] if (self.carry_search_state and fp.slice_type == _engine.SLICE_P) else None
+            _, rec, out = eng.init_picture(first, f, fp.qp, self.layout, params=fp, col=col, search_state=state, **kw)
             res.append({"poc": poc, "slice_type": fp.slice_type, "qp": fp.qp, "lambda": fp.lambda_, "out": out, "rec": rec, "first": first})
+        eng.compress_pictures(0, self.n_clips, self.layout)
         if self.wpp:
-            eng.compress_wpp(0, self.n_clips * self.n_chains)
             for s, r in enumerate(res):                      # HM's state after the picture: the last row's (fcu_wpp_begin_p)
                 r["search_state"] = eng.search_state(r["first"] + self.n_chains - 1)      # (sliced: the state after the last slice)
-                self.search_state[s] = r["search_state"] if (self.slice_rows is None and self.tiles is None) else None
-        elif self.tiles is not None:
-            eng.compress_chains(0, self.n_clips * self.n_chains, eng.n_ctu)      # every tile to its end
-        else:
-            eng.compress_chains(0, self.n_clips * self.n_slices, self.slice_ctus)
+                self.search_state[s] = r["search_state"] if self.carry_search_state else None
         for s, r in enumerate(res):
             r["rec_unfiltered"] = [p.clone() for p in r["rec"]]
             if self.do_deblock:
-                eng.deblock(r["first"], tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
+                eng.deblock(r["first"], layout=self.layout)
         if self.do_sao:
             layer = _engine.ldp_layer(poc)
-            pics = [{"org": eng._keep[r["first"]][0], "rec": r["rec"], "qp": fp.qp, "lambda_": fp.lambda_, "slice_type": fp.slice_type,
+            pics = [{"org": eng.org_planes(r["first"]), "rec": r["rec"], "qp": fp.qp, "lambda_": fp.lambda_, "slice_type": fp.slice_type,
                      "slice_ctus": self.sao_slice_ctus, "enabled": self.sao_rate[s].enabled(layer)} for s, r in enumerate(res)]
-            coded, off, _ = eng.sao(pics, tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
+            coded, off, _ = eng.sao(pics, layout=self.layout)
             for s, r in enumerate(res):
                 r["sao"], r["sao_enabled"] = coded[s], pics[s]["enabled"]
                 self.sao_rate[s].update(layer, off[s], eng.n_ctu)
         if self.do_report:                                   # on the final planes: after the loop filters that are enabled
-            for r, rep in zip(res, eng.report([{"org": eng._keep[r["first"]][0], "rec": r["rec"], "out": r["out"]} for r in res])):
+            for r, rep in zip(res, eng.report([{"org": eng.org_planes(r["first"]), "rec": r["rec"], "out": r["out"]} for r in res])):
                 r["report"] = rep
         for s, r in enumerate(res):
             self.col[s] = r["out"]                           # stays in HBM: the next picture's collocated motion field

@@ -16,6 +16,7 @@ torch is plumbing (device buffers); there is no CPU fallback for the decisions.
 import numpy as np
 
 from . import engine as _engine
+from .layout import PictureLayout
 
 TRAINING, VERIFYING, TESTING = _engine.TRAINING, _engine.VERIFYING, _engine.TESTING
 
@@ -84,55 +85,26 @@ class SequenceDecider:
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
         run as concurrent chains, but every slice start cuts the intra neighbourhood and resets CABAC.
         wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains, each row waiting for the row above
-        (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.  Cannot be combined with slice_ctus.
+        (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.
         slice_rows (with wpp only): WaveFrontSynchro together with SliceMode 1, SliceArgument = slice_rows x the picture width in
         CTUs -- independent slices of slice_rows whole CTU rows whose rows run as chains (fcu_wpp_begin_slices): the first row of
         a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1).
         tiles=(C, R): one slice per picture cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
         (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  lf_cross_tiles (with tiles
         only): LFCrossTileBoundaryFlag of the deblocking, 0 or 1 (fcu_deblock_tiles); None means 1, HM's default -- deblocking
-        crosses the tile boundaries.  Not with slice_ctus / slice_rows.  This driver runs no SAO: sao=True together with
-        tiles is refused whatever lf_cross_tiles says.
+        crosses the tile boundaries.  PictureLayout holds the rules of these combinations.  This driver runs no SAO: sao=True
+        together with tiles is refused whatever lf_cross_tiles says.
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
         statistics) of the final planes, taken on the device in one batched call for the pictures of a group."""
         self.do_report = report
         sao = flags.get("sao")
-        if tiles is not None:
-            if slice_ctus or slice_rows is not None:
-                raise ValueError("SequenceDecider: tiles need one slice per picture (no slice_ctus, no slice_rows)")
-            if lf_cross_tiles is not None and lf_cross_tiles not in (0, 1):
-                raise ValueError("SequenceDecider: lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1")
-            if sao and lf_cross_tiles is None:
-                raise ValueError("SequenceDecider: sao=True together with tiles needs lf_cross_tiles=0 or 1 -- and this driver runs no SAO (LowDelayPDecider does)")
-            if sao:
-                raise ValueError("SequenceDecider: sao=True is not supported: this driver runs no SAO (LowDelayPDecider(tiles=..., sao=True, lf_cross_tiles=...) does)")
-            _engine.tile_grid((width + 63) // 64, (height + 63) // 64, *tiles)      # ValueError for a grid with an empty tile
-        elif lf_cross_tiles is not None:
-            raise ValueError("SequenceDecider: lf_cross_tiles is the deblocking flag of a picture with tiles and needs tiles=(C, R)")
-        self.tiles = tiles
-        self.lf_cross_tiles = 1 if lf_cross_tiles is None else lf_cross_tiles
-        if wpp and slice_ctus:
-            raise ValueError("SequenceDecider: wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
-        if slice_rows is not None and not wpp:
-            raise ValueError("SequenceDecider: slice_rows cuts a WaveFrontSynchro picture into slices of whole CTU rows and needs wpp=True (without WPP: slice_ctus)")
-        if slice_rows is not None and slice_rows < 1:
-            raise ValueError("SequenceDecider: slice_rows must be at least 1")
-        self.wpp, self.slice_rows = wpp, slice_rows
+        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, who="SequenceDecider")
+        if sao and tiles is not None:
+            raise ValueError("SequenceDecider: sao=True is not supported: this driver runs no SAO (LowDelayPDecider(tiles=..., sao=True, lf_cross_tiles=...) does)")
+        self.tiles, self.lf_cross_tiles, self.wpp, self.slice_rows, self.slice_ctus = tiles, lo.lf_cross_tiles, wpp, slice_rows, lo.slice_ctus
+        self.slice_mode, self.n_slices = lo.describe(), lo.chains      # n_slices: chains per picture (slices, rows or tile chains)
         self.width, self.height, self.qp, self.fast, self.do_deblock, self.flags = width, height, qp, fast, deblock, flags
         self.in_flight = max(1, in_flight)
-        w_ctu = (width + 63) // 64
-        n_ctu = w_ctu * ((height + 63) // 64)
-        self.slice_ctus = slice_ctus if slice_ctus else n_ctu
-        self.slice_mode = "SliceMode 0 (one slice per picture)" if self.slice_ctus >= n_ctu else f"SliceMode 1, SliceArgument {self.slice_ctus}"
-        self.n_slices = (n_ctu + self.slice_ctus - 1) // self.slice_ctus
-        if wpp:
-            if slice_rows is not None:
-                self.slice_mode = f"SliceMode 1, SliceArgument {slice_rows * w_ctu}"
-            self.slice_mode += ", WaveFrontSynchro"
-            self.n_slices = (height + 63) // 64                 # chains per picture: one per CTU row
-        if tiles is not None:
-            self.slice_mode = f"SliceMode 0 (one slice per picture), {tiles[0]} x {tiles[1]} uniform tiles" + (", WaveFrontSynchro" if wpp else "")
-            self.n_slices = tiles[0] * ((height + 63) // 64 if wpp else tiles[1])      # chains per picture (fcu_tile_chains)
         self.eng = _engine.CuEngine(width, height, max_chains=self.n_slices * self.in_flight, device=device)
         self.schedule = schedule or FastDecisionSchedule()
         self.poc = 0
@@ -161,30 +133,22 @@ class SequenceDecider:
             poc = self.poc + i
             state, sk, te = self.schedule.begin_picture(poc) if self.fast else (TRAINING, np.zeros(4, np.uint8), np.zeros(4, np.uint8))
             first = i * self.n_slices
-            if self.tiles is not None:
-                n_sl, rec, out = eng.init_tile_picture(first, yuv, self.qp, *self.tiles, wpp=self.wpp, **self.flags)
-            elif self.wpp:
-                n_sl, rec, out = eng.init_wpp_picture(first, yuv, self.qp, slice_rows=self.slice_rows, **self.flags)
-            else:
-                n_sl, rec, out = eng.init_slice_chains(first, yuv, self.qp, self.slice_ctus, **self.flags)
+            n_sl, rec, out = eng.init_picture(first, yuv, self.qp, self.layout, **self.flags)
             if state != TRAINING:
-                obf = eng.obf_prepass(eng._keep[first][0][0])[0][0].contiguous()
+                obf = eng.obf_prepass(eng.org_planes(first)[0])[0][0].contiguous()
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
-        if self.wpp:
-            eng.compress_wpp(0, len(yuvs) * self.n_slices)
-        else:
-            eng.compress_chains(0, len(yuvs) * self.n_slices, self.slice_ctus)      # (tiles: slice_ctus = the picture, every tile runs to its end)
+        eng.compress_pictures(0, len(yuvs), self.layout)
         nb = _engine.CTU_OUT_BYTES
         for p in pics:
             p["verify"] = eng.verify_counts(p["first"], self.n_slices) if p["state"] == VERIFYING else None
             if self.fast:
                 self.schedule.end_picture(p["poc"], p["verify"])
             if self.do_deblock:
-                eng.deblock(p["first"], tiles=self.tiles, lf_cross_tiles=self.lf_cross_tiles)
+                eng.deblock(p["first"], layout=self.layout)
         if self.do_report:                                   # on the final planes: after the deblocking when it is enabled
-            for p, rep in zip(pics, eng.report([{"org": eng._keep[p["first"]][0], "rec": p["rec"], "out": p["out"]} for p in pics])):
+            for p, rep in zip(pics, eng.report([{"org": eng.org_planes(p["first"]), "rec": p["rec"], "out": p["out"]} for p in pics])):
                 p["report"] = rep
         eng.sync()
         for p in pics:

@@ -55,25 +55,22 @@ def main():
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
-    if args.slice_rows is not None and not args.wpp:
-        ap.error("--slice-rows needs --wpp (without WaveFrontSynchro: --slice-ctus / --row-slices)")
     tiles = None
-    if args.lf_cross_tiles is not None and args.tiles is None:
-        ap.error("--lf-cross-tiles needs --tiles")
     if args.tiles is not None:
         try:
             tiles = tuple(int(v) for v in args.tiles.lower().split("x"))
             assert len(tiles) == 2
         except (ValueError, AssertionError):
             ap.error("--tiles takes COLUMNSxROWS, e.g. 4x2")
-        if args.slice_ctus or args.row_slices or args.slice_rows is not None:
-            ap.error("--tiles needs one slice per picture (no --slice-ctus / --row-slices / --slice-rows)")
     import __graft_entry__ as g
     pkg = g.load_package()
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
-    dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report,
-                              schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
+    try:                                                       # the rules of these combinations: PictureLayout
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report,
+                                  schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
+    except ValueError as e:
+        ap.error(str(e))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
     depths = []
