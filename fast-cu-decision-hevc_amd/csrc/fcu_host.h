@@ -3,11 +3,17 @@
  * slice with libm (lambda, sqrt(lambda), chroma distortion weight, RDOQ lambdas, RDOQ error
  * scales, sign-hiding rdFactor).  They are handed to the kernels as f64/i64 bit patterns so
  * that no transcendental is ever evaluated on the device.
- * Also the host-side fills of the chain descriptor (chain_bind ... wpp_bind_row, tile_bind), the one copy
- * libfcu.so and the test-only emulators bind a chain with.
+ * Also the host-side fills of the chain descriptor (chain_bind ... wpp_bind_row, tile_bind) and, at the end, HostState: the
+ * host state machine of libfcu.so -- every argument and state rule of the chain entry points, the one picture binder and the
+ * two launch guards, on the host descriptors alone.  No HIP header, no HIP call: libfcu.so (fcu_kernels.hip adds the device
+ * copies and the launches), the test-only emulators and tests/emu/host_emu.cpp share this one copy, and the CPU suite runs the
+ * rules (tests/test_host_rules.py).
  */
 #pragma once
 #include <math.h>
+#include <stddef.h>
+#include <string>
+#include <vector>
 #include "fcu_engine.h"
 
 namespace fcu {
@@ -81,7 +87,7 @@ inline void ldp_slice(fcu_frame_params &fp, int base_qp, int poc)
 }
 
 /* ---- The host-side fills of the chain descriptor.  Plain pointers in, fields out, no HIP call: the entry points of libfcu.so
- * (fcu_kernels.hip: the checks, the error texts, the copies to the device) and the test-only emulator drivers (tests/emu, built
+ * (HostState below: the checks and the error texts; fcu_kernels.hip: the copies to the device) and the test-only emulator drivers (tests/emu, built
  * with -DFCU_EMU) bind a chain through these functions and through nothing else. */
 
 /* fcu_chain_begin: a zeroed descriptor, the slice's parameters, the planes of a width x height picture and its output array;
@@ -232,5 +238,216 @@ inline double report_psnr(uint64_t ssd, uint64_t n)
   const double ref = 255.0 * 255.0 * (double)n;
   return ssd ? 10.0 * log10(ref / (double)ssd) : 999.99;
 }
+
+/* ---- The byte ranges { offset, length } of the descriptor libfcu.so copies to the device on their own, named once: a setter
+ * uploads the range it has written and nothing else, so a chain's position, coder state and counters on the device stay. */
+struct ChainRange { size_t off, len; };
+constexpr ChainRange CR_ALL = { 0, sizeof(Chain) };
+constexpr ChainRange CR_REF = { offsetof(Chain, ref), 3 * sizeof(void *) + 3 * sizeof(int) };      /* ref, ref_stride */
+static_assert(offsetof(Chain, ref_stride) == offsetof(Chain, ref) + 3 * sizeof(void *) && offsetof(Chain, out) >= offsetof(Chain, ref_stride) + 3 * sizeof(int), "ref / ref_stride are adjacent, out follows");
+constexpr ChainRange CR_LIST0 = { offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs) };      /* refs .. col_ref_poc: list 0 and the collocated POCs, not the search state */
+static_assert(offsetof(Chain, refs) < offsetof(Chain, n_ref) && offsetof(Chain, col_ref_poc) + sizeof(int) * FCU_MAX_REF == offsetof(Chain, int_mv_r), "refs .. col_ref_poc end where int_mv_r starts");
+constexpr ChainRange CR_RANGE = { offsetof(Chain, next_ctu), 2 * sizeof(int) };      /* next_ctu, end_ctu */
+static_assert(offsetof(Chain, end_ctu) == offsetof(Chain, next_ctu) + sizeof(int), "next_ctu / end_ctu are adjacent");
+constexpr ChainRange CR_DECISION = { offsetof(Chain, dec_state), sizeof(Chain) - offsetof(Chain, dec_state) };      /* dec_state .. the end */
+static_assert(offsetof(Chain, dec_state) > offsetof(Chain, prof) && offsetof(Chain, dec_state) > offsetof(Chain, state), "the decision block lies behind the coder state and the counters");
+constexpr ChainRange CR_COL = { offsetof(Chain, col), sizeof(void *) };
+static_assert(sizeof(((Chain *)0)->col) == sizeof(void *), "col is one pointer");
+constexpr ChainRange CR_PU_TRACE = { offsetof(Chain, pu_trace), sizeof(void *) };
+static_assert(sizeof(((Chain *)0)->pu_trace) == sizeof(void *), "pu_trace is one pointer");
+constexpr ChainRange CR_INT_MV = { offsetof(Chain, int_mv_r), 2 * FCU_MAX_REF * sizeof(int32_t) };
+static_assert(sizeof(((Chain *)0)->int_mv_r) == 2 * FCU_MAX_REF * sizeof(int32_t), "search state layout");
+
+/* the rows of a P picture decide one picture: every row must name row 0's reference pictures and collocated field */
+inline bool wpp_same_refs(const Chain &a, const Chain &b)
+{
+  if (a.n_ref != b.n_ref || a.poc != b.poc || a.col != b.col || a.col_poc != b.col_poc || a.ref_stride[0] != b.ref_stride[0]) return false;
+  for (int k = 0; k < 3; k++) if (a.ref[k] != b.ref[k]) return false;
+  for (int r = 0; r < FCU_MAX_REF; r++) {
+    if (a.col_ref_poc[r] != b.col_ref_poc[r]) return false;
+    if (r >= a.n_ref) continue;
+    if (a.ref_poc[r] != b.ref_poc[r]) return false;
+    for (int k = 0; k < 3; k++) if (a.refs[r][k] != b.refs[r][k]) return false;
+  }
+  return true;
+}
+
+/* ---- The host state machine.  planes of a picture as the binders take them */
+struct Planes { const uint8_t *oy, *ou, *ov; uint8_t *ry, *ru, *rv; fcu_ctu_out *out; };
+
+/* how a binder cuts a picture into chains, and the entry point it speaks for in the messages: the rows of a one-slice picture
+ * (fcu_wpp_begin: I slices only, fcu_wpp_begin_p: P slices only), rows of slices of slice_rows whole CTU rows
+ * (fcu_wpp_begin_slices), one chain per tile (fcu_tiles_begin), rows inside tiles (fcu_wpp_begin_tiles) */
+struct PictureCut {
+  const char *name; int only_type; bool sliced; int slice_rows; bool tiled; int n_cols, n_rows, wpp;
+  static PictureCut rows(int slice_type) { return { slice_type == FCU_SLICE_P ? "fcu_wpp_begin_p" : "fcu_wpp_begin", slice_type, false, 0, false, 0, 0, 1 }; }
+  static PictureCut row_slices(int slice_rows) { return { "fcu_wpp_begin_slices", -1, true, slice_rows, false, 0, 0, 1 }; }
+  static PictureCut tiles(int n_cols, int n_rows, int wpp) { return { wpp ? "fcu_wpp_begin_tiles" : "fcu_tiles_begin", -1, false, 0, true, n_cols, n_rows, wpp }; }
+};
+
+/* The sequence parameters, the host copy of every chain's descriptor and every chain's position (where the launches so far
+ * have left it).  A method that can refuse returns the FCU_* code and leaves the text, which names the entry point, in `err`. */
+struct HostState {
+  fcu_seq_params sp = {};
+  int w_ctu = 0, h_ctu = 0, n_ctu = 0;           /* the picture in CTUs: computed here and nowhere else */
+  std::vector<Chain> chains;
+  std::vector<int> pos;
+  struct Picture { int first, n; };               /* per chain: the chains [first, first + n) picture_bind last filled together with it */
+  std::vector<Picture> pic;
+  std::string err;
+
+  int refuse(int code, const std::string &msg) { err = msg; return code; }
+  static bool seq_ok(const fcu_seq_params *s) { return s && s->width > 0 && s->height > 0 && !(s->width & 7) && !(s->height & 7) && s->max_chains > 0; }
+  void init(const fcu_seq_params &s)
+  {
+    sp = s; w_ctu = (s.width + 63) / 64; h_ctu = (s.height + 63) / 64; n_ctu = w_ctu * h_ctu;
+    chains.resize((size_t)s.max_chains);
+    memset(chains.data(), 0, sizeof(Chain) * chains.size());
+    pos.assign((size_t)s.max_chains, 0);
+    pic.assign((size_t)s.max_chains, Picture{ 0, 0 });
+  }
+  bool has(int chain) const { return chain >= 0 && chain < sp.max_chains; }
+  int position(int chain) const { return has(chain) ? pos[(size_t)chain] : -1; }
+  /* what every setter of a bound chain's state asks first */
+  int bound(const char *name, int chain)
+  {
+    if (!has(chain)) return refuse(FCU_ERR_ARG, std::string(name) + ": bad argument");
+    if (chains[(size_t)chain].out == nullptr) return refuse(FCU_ERR_STATE, std::string(name) + ": chain not bound (fcu_chain_begin)");
+    return FCU_OK;
+  }
+
+  /* fcu_chain_begin: the argument checks, then the descriptor of a chain that decides the whole picture from CTU 0 */
+  int chain_begin_check(int chain, const fcu_frame_params *fp, const Planes &pl)
+  {
+    if (!fp || !has(chain) || !pl.oy || !pl.ou || !pl.ov || !pl.ry || !pl.ru || !pl.rv || !pl.out) return refuse(FCU_ERR_ARG, "fcu_chain_begin: bad argument");
+    if (fp->qp < 0 || fp->qp > 51 || fp->slice_ctus < 0) return refuse(FCU_ERR_ARG, "fcu_chain_begin: QP / slice_ctus out of range");
+    if (fp->slice_type != FCU_SLICE_I && fp->slice_type != FCU_SLICE_P) return refuse(FCU_ERR_ARG, "fcu_chain_begin: unknown slice type");
+    if (fp->slice_type == FCU_SLICE_P && (!(fp->lambda > 0.0) || fp->search_range < 1 || fp->search_range > 64)) return refuse(FCU_ERR_ARG, "fcu_chain_begin: a P slice needs its lambda (fcu_ldp_slice) and 1 <= search_range <= 64");
+    return FCU_OK;
+  }
+  int chain_begin(int chain, const fcu_frame_params *fp, const Planes &pl)
+  {
+    if (const int rc = chain_begin_check(chain, fp, pl)) return rc;
+    chain_bind(chains[(size_t)chain], sp.width, sp.height, *fp, pl.oy, pl.ou, pl.ov, pl.ry, pl.ru, pl.rv, pl.out);
+    pos[(size_t)chain] = 0;
+    return FCU_OK;
+  }
+
+  /* ---- the picture binder.  picture_check: everything the five picture entry points refuse, in their order (libfcu.so allocates
+   * the WaveFrontSynchro blocks between the two steps); picture_bind: the descriptors and positions of the picture's chains
+   * [first, first + n), returns n.  A row that starts a slice, and row 0 of a tile, is bound as row 0 of a picture is: no row
+   * above (wpp_above -1), no sync slot to read -- run_wpp_chain waits for and inherits nothing, compress_ctu resets the coder. */
+  int picture_chains(const PictureCut &cut) const { return cut.tiled ? tile_chains(w_ctu, h_ctu, cut.n_cols, cut.n_rows, cut.wpp) : h_ctu; }
+  int picture_check(const PictureCut &cut, int first, const fcu_frame_params *fp, const Planes &pl)
+  {
+    const std::string name(cut.name);
+    if (!fp) return refuse(FCU_ERR_ARG, name + ": bad argument");
+    if (cut.only_type == FCU_SLICE_I && fp->slice_type != FCU_SLICE_I) return refuse(FCU_ERR_ARG, name + ": binds I slices only (P slices: fcu_wpp_begin_p)");
+    if (cut.only_type == FCU_SLICE_P && fp->slice_type != FCU_SLICE_P) return refuse(FCU_ERR_ARG, name + ": binds P slices only (I slices: fcu_wpp_begin)");
+    fcu_frame_params f = *fp;
+    if (cut.tiled) {
+      if (!tile_grid(w_ctu, h_ctu, cut.n_cols, cut.n_rows, nullptr, nullptr)) return refuse(FCU_ERR_ARG, name + ": a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
+      if (fp->slice_ctus != 0) return refuse(FCU_ERR_ARG, name + ": tiles need one slice per picture (slice_ctus 0)");
+      if (!tile_params_ok(*fp, cut.n_cols)) return refuse(FCU_ERR_ARG, name + ": TMVP across tile columns is not supported (tmvp 1 needs n_cols 1)");
+      if (first < 0 || first + picture_chains(cut) > sp.max_chains) return refuse(FCU_ERR_ARG, name + ": too few chains (fcu_tile_chains)");
+    } else {
+      if (cut.sliced && cut.slice_rows < 1) return refuse(FCU_ERR_ARG, name + ": slice_rows must be at least 1");
+      if (!cut.sliced && fp->slice_ctus != 0) return refuse(FCU_ERR_ARG, name + ": WaveFrontSynchro needs one slice per picture (slice_ctus 0); slices of whole CTU rows are bound by fcu_wpp_begin_slices");
+      if (cut.sliced && (f.slice_ctus = wpp_slice_ctus(w_ctu, cut.slice_rows, fp->slice_ctus)) < 0) return refuse(FCU_ERR_ARG, name + ": slice_rows must be >= 1 and slice_ctus 0 or slice_rows x the picture width in CTUs (a slice starts at a row start)");
+      if (first < 0 || first + h_ctu > sp.max_chains) return refuse(FCU_ERR_ARG, name + ": too few chains for one chain per CTU row (fcu_wpp_rows)");
+    }
+    return chain_begin_check(first, &f, pl);
+  }
+  /* (arguments picture_check has accepted; sync = slot 0 of the sync slot array, used with cut.wpp only) */
+  int picture_bind(const PictureCut &cut, int first, const fcu_frame_params &fp, const Planes &pl, uint8_t *sync)
+  {
+    fcu_frame_params f = fp;
+    if (cut.sliced) f.slice_ctus = wpp_slice_ctus(w_ctu, cut.slice_rows, fp.slice_ctus);
+    Chain base;
+    chain_bind(base, sp.width, sp.height, f, pl.oy, pl.ou, pl.ov, pl.ry, pl.ru, pl.rv, pl.out);
+    const int n_cols = cut.tiled ? cut.n_cols : 1, n_rows = cut.tiled ? cut.n_rows : 1;      /* no tiles: one tile, the picture */
+    std::vector<int> cb((size_t)n_cols + 1), rb((size_t)n_rows + 1);
+    tile_grid(w_ctu, h_ctu, n_cols, n_rows, cb.data(), rb.data());
+    int i = first;
+    for (int ty = 0; ty < n_rows; ty++) for (int tx = 0; tx < n_cols; tx++) {      /* tile-scan order */
+      const int x0 = cb[(size_t)tx], y0 = rb[(size_t)ty], tw = cb[(size_t)tx + 1] - x0, th = rb[(size_t)ty + 1] - y0;
+      for (int r = 0; r < (cut.wpp ? th : 1); r++, i++) {
+        Chain &h = chains[(size_t)i];
+        h = base;
+        if (cut.tiled) tile_bind(h, x0, y0, tw, th);
+        if (cut.wpp && cut.tiled) wpp_bind_tile_row(h, r, i, sync);
+        else if (cut.wpp) wpp_bind_row(h, r, w_ctu, cut.sliced ? cut.slice_rows : 0, first, sync);
+        pos[(size_t)i] = h.next_ctu;
+      }
+    }
+    for (int k = first; k < i; k++) pic[(size_t)k] = Picture{ first, i - first };
+    return i - first;
+  }
+
+  /* fcu_chain_set_range: the state checks before the range checks */
+  int set_range(int chain, int first_ctu, int n_ctus)
+  {
+    if (!has(chain)) return refuse(FCU_ERR_ARG, "fcu_chain_set_range: bad argument");
+    Chain &h = chains[(size_t)chain];
+    if (h.out == nullptr) return refuse(FCU_ERR_STATE, "fcu_chain_set_range: chain not bound (fcu_chain_begin)");
+    if (h.wpp) return refuse(FCU_ERR_STATE, "fcu_chain_set_range: a WaveFrontSynchro row chain keeps the row fcu_wpp_begin gave it");
+    if (!tile_is_picture(h)) return refuse(FCU_ERR_STATE, "fcu_chain_set_range: a tile chain keeps the tile fcu_tiles_begin gave it");
+    const int sl = h.p.slice_ctus;
+    if (first_ctu < 0 || n_ctus <= 0 || first_ctu + n_ctus > h.n_ctu) return refuse(FCU_ERR_ARG, "fcu_chain_set_range: range outside the frame");
+    /* a chain may only start where the reference resets its entropy coder and cuts the neighbourhood: at a slice start */
+    if (first_ctu != 0 && (sl <= 0 || first_ctu % sl != 0)) return refuse(FCU_ERR_ARG, "fcu_chain_set_range: a chain must start at a slice boundary");
+    if (first_ctu + n_ctus != h.n_ctu && (sl <= 0 || (first_ctu + n_ctus) % sl != 0)) return refuse(FCU_ERR_ARG, "fcu_chain_set_range: a chain must end at a slice boundary");
+    h.next_ctu = first_ctu; h.end_ctu = first_ctu + n_ctus;
+    pos[(size_t)chain] = first_ctu;
+    return FCU_OK;
+  }
+
+  /* fcu_compress_ctu's own rule (a tile chain's position counts CTUs inside its tile; the CTU is named by its picture address) */
+  int ctu_check(int chain, uint32_t ctuRsAddr)
+  {
+    if (!has(chain)) return refuse(FCU_ERR_ARG, "fcu_compress_ctu: bad argument");
+    const Chain &h = chains[(size_t)chain];
+    if (pos[(size_t)chain] >= h.end_ctu || h.out == nullptr || (int)ctuRsAddr != tile_ctu_addr(h, pos[(size_t)chain])) return refuse(FCU_ERR_STATE, "fcu_compress_ctu: CTUs of a chain must be decided in raster order");
+    return FCU_OK;
+  }
+
+  /* fcu_compress_chains: the guard of the launch, and the positions after it */
+  int chains_check(int first, int n, int ctus)
+  {
+    if (first < 0 || n <= 0 || first + n > sp.max_chains || ctus <= 0) return refuse(FCU_ERR_ARG, "fcu_compress_chains: bad range");
+    for (int i = first; i < first + n; i++) {
+      const Chain &h = chains[(size_t)i];
+      if (h.out == nullptr) return refuse(FCU_ERR_STATE, "fcu_compress_chains: chain not bound (fcu_chain_begin)");
+      if (h.wpp) return refuse(FCU_ERR_STATE, "fcu_compress_chains: a WaveFrontSynchro row chain is decided by fcu_compress_wpp");
+      if (h.p.slice_type == SLICE_P && h.ref[0] == nullptr) return refuse(FCU_ERR_STATE, "fcu_compress_chains: P chain without reference picture (fcu_chain_set_reference)");
+    }
+    return FCU_OK;
+  }
+  void chains_launched(int first, int n, int ctus) { for (int i = first; i < first + n; i++) { int &p = pos[(size_t)i]; p += ctus; if (p > chains[(size_t)i].end_ctu) p = chains[(size_t)i].end_ctu; } }
+
+  /* fcu_compress_wpp: the guard of the WaveFrontSynchro launch.  A row waits for the chain its descriptor names, and for ever if
+   * that chain is not in the launch: the range must hold whole pictures, each as picture_bind made it (`pic`) and not yet decided.
+   * A chain bound again since -- by fcu_chain_begin (no row chain any more) or as part of another picture (another record) --
+   * breaks its old picture until that is bound again as a whole. */
+  int wpp_check(int first, int n)
+  {
+    if (first < 0 || n <= 0 || first + n > sp.max_chains) return refuse(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
+    for (int i = first, start = first, end = first; i < first + n; i++) {
+      const Chain &h = chains[(size_t)i];
+      const Picture &p = pic[(size_t)i];
+      if (h.out == nullptr || !h.wpp) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles");
+      if (i == end) { start = i; end = i + p.n; }             /* a picture must start here: chain i is its first, the rest carry its record */
+      if (p.first != start || p.n != end - start) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles, their rows at consecutive chains (tiles: in tile-scan order, the rows of a tile top to bottom)");
+      if (end > first + n) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture (tiles: of its last tile)");
+      if (pos[(size_t)i] != h.next_ctu) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles)");
+      if (h.p.slice_type == SLICE_P) {
+        if (h.ref[0] == nullptr) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: P row without reference picture (fcu_chain_set_reference(s) on every row)");
+        if (!wpp_same_refs(h, chains[(size_t)p.first])) return refuse(FCU_ERR_STATE, "fcu_compress_wpp: the rows of a P picture name different reference pictures or collocated fields");
+      }
+    }
+    return FCU_OK;
+  }
+  void wpp_launched(int first, int n) { for (int i = first; i < first + n; i++) pos[(size_t)i] = chains[(size_t)i].end_ctu; }
+};
 
 } // namespace fcu

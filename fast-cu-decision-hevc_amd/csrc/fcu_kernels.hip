@@ -45,7 +45,7 @@ fcu_ctu_engine(Chain *chains, Scratch *scratch, int first, int ctus)
 /* WaveFrontSynchro: the row chains [first, first + gridDim.x) of whole pictures, one launch.  A wave takes a ticket and decides
  * chain first + ticket: the rows of a picture are bound top to bottom at increasing chain indices, so the chain a wave waits on
  * holds an earlier ticket and is already running (or done) -- no deadlock whatever the dispatch order, and the launch may hold
- * more chains than are resident.  ctl: fcu_ctx::d_wpp_ctl, zeroed before every launch. */
+ * more chains than are resident.  ctl: fcu_ctx::wpp_ctl, zeroed before every launch. */
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FCU_WAVES_PER_EU, FCU_WAVES_PER_EU)))
 fcu_ctu_engine_wpp(Chain *chains, Scratch *scratch, unsigned *ctl, int first)
 {
@@ -74,24 +74,51 @@ __global__ void __launch_bounds__(256) fcu_pad_plane(const uint8_t *src, int w, 
 }
 
 /* ---------------------------------------------------------------------------------------- */
+/* one buffer per host thread: a failure text never races with another thread's call */
+static thread_local char g_err[256] = "";
+static int fail(int code, const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return code; }
+static int fail(int code, const std::string &msg) { return fail(code, msg.c_str()); }
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: %s", #x, hipGetErrorString(e_)); return FCU_ERR_HIP; } } while (0)
+#define CHK(x) do { const int rc_ = (x); if (rc_ != FCU_OK) return rc_; } while (0)
+/* the first step of an entry point: the rule of fcu_host.h on the host state, its code and text on a refusal */
+#define HOST(null_msg, call) do { if (!c) return fail(FCU_ERR_ARG, null_msg); const int rc_ = c->hs.call; if (rc_ != FCU_OK) return fail(rc_, c->hs.err); } while (0)
+
+/* a device block of the context that only grows: no allocation in the steady state.  The old block may still be read by work
+ * queued on the stream, so the stream is drained before it is freed. */
+struct DevBuf {
+  void *p = nullptr; size_t cap = 0;
+  hipError_t reserve(size_t bytes, hipStream_t st)
+  {
+    if (bytes <= cap) return hipSuccess;
+    if (p) { const hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) return e; hipFree(p); p = nullptr; cap = 0; }
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+};
+
+/* the events a call times its kernels with: created and recorded only when `on` (the caller asked for times), destroyed on
+ * every return */
+struct Events {
+  hipStream_t st; bool on; hipEvent_t e[5] = {};
+  Events(hipStream_t st_, bool on_) : st(st_), on(on_) {}
+  ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); }
+  hipError_t create(int n) { for (int i = 0; on && i < n; i++) { const hipError_t r = hipEventCreate(&e[i]); if (r != hipSuccess) return r; } return hipSuccess; }
+  hipError_t record(int i) { return on ? hipEventRecord(e[i], st) : hipSuccess; }
+  void ms(float *out, int i, int j) { if (on) hipEventElapsedTime(out, e[i], e[j]); }
+};
+
 struct fcu_ctx {
-  fcu_seq_params sp;
-  int n_ctu;
-  Chain *d_chains; Scratch *d_scratch;
-  std::vector<Chain> h_chains;
-  std::vector<int> h_pos;
+  HostState hs;                    /* sequence parameters, host descriptors, positions -- and every rule on them (fcu_host.h) */
+  Chain *d_chains = nullptr; Scratch *d_scratch = nullptr;
   std::vector<hipEvent_t> ev;      /* start/stop pairs of launches not yet harvested (bounded, see harvest_events) */
-  double ms_acc; int launches;
-  /* persistent scratch of fcu_obf_prepass (grown on demand, freed by fcu_destroy) */
-  unsigned *d_hist; size_t hist_cap; int *d_thr; size_t thr_cap;
-  /* persistent scratch of fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
-  void *d_sao; size_t sao_cap;
-  /* persistent scratch of fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
-  void *d_rep; size_t rep_cap;
-  /* WaveFrontSynchro (allocated by the first fcu_wpp_begin): d_wpp_ctl = the words a launch polls (ticket, abort, one progress
-   * word per chain), a block of its own from the allocation's start, wpp_ctl_bytes a multiple of 16, zeroed before every launch;
-   * d_wpp_sync = one sync slot of WPP_SYNC_BYTES per chain */
-  unsigned *d_wpp_ctl; size_t wpp_ctl_bytes; uint8_t *d_wpp_sync;
+  double ms_acc = 0; int launches = 0;
+  DevBuf hist, thr;                /* fcu_obf_prepass: histograms, thresholds */
+  DevBuf sao;                      /* fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
+  DevBuf rep;                      /* fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
+  /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
+   * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
+  DevBuf wpp_ctl, wpp_sync;
 };
 
 /* Launch timing keeps two events per launch until they are read.  A long-running caller that never asks for
@@ -108,12 +135,39 @@ static void harvest_events(fcu_ctx *c, size_t keep_pairs)
     c->ev.erase(c->ev.begin(), c->ev.begin() + 2);
   }
 }
+/* an engine launch between its two events */
+template <class Launch> static int timed_launch(fcu_ctx *c, hipStream_t st, Launch launch)
+{
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  HIPCHK(hipEventRecord(e0, st));
+  launch();
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e1, st));
+  c->ev.push_back(e0); c->ev.push_back(e1);
+  harvest_events(c, FCU_MAX_PENDING_EVENTS);
+  return FCU_OK;
+}
 
-/* one buffer per host thread: a failure text never races with another thread's call */
-static thread_local char g_err[256] = "";
-static int fail(int code, const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); return code; }
-static int fail(int code, const std::string &msg) { return fail(code, msg.c_str()); }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: %s", #x, hipGetErrorString(e_)); return FCU_ERR_HIP; } } while (0)
+/* every copy into d_chains: the byte range r (fcu_host.h) of the host descriptors of chains [first, first + n) -- or, with
+ * src, the caller's bytes for that range.  sync_first: the chains may be running, the device is drained before the copy. */
+static int upload(fcu_ctx *c, int first, int n, ChainRange r, bool sync_first, const void *src = nullptr)
+{
+  if (sync_first) HIPCHK(hipDeviceSynchronize());
+  if (r.len == sizeof(Chain)) { HIPCHK(hipMemcpy(&c->d_chains[first], &c->hs.chains[(size_t)first], sizeof(Chain) * (size_t)n, hipMemcpyHostToDevice)); return FCU_OK; }
+  for (int i = first; i < first + n; i++)
+    HIPCHK(hipMemcpy((char *)&c->d_chains[i] + r.off, src ? src : (const char *)&c->hs.chains[(size_t)i] + r.off, r.len, hipMemcpyHostToDevice));
+  return FCU_OK;
+}
+/* ... and every whole descriptor back, after the device has finished */
+static int read_back(fcu_ctx *c, int first, int n, std::vector<Chain> &h)
+{
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  HIPCHK(hipDeviceSynchronize());
+  h.resize((size_t)n);
+  HIPCHK(hipMemcpy(h.data(), &c->d_chains[first], sizeof(Chain) * (size_t)n, hipMemcpyDeviceToHost));
+  return FCU_OK;
+}
 
 extern "C" {
 
@@ -152,23 +206,17 @@ void fcu_default_frame_params(fcu_frame_params *fp, int qp) { default_frame_para
 
 int fcu_create(const fcu_seq_params *sp, fcu_ctx **out)
 {
-  if (!sp || !out || sp->width <= 0 || sp->height <= 0 || (sp->width & 7) || (sp->height & 7) || sp->max_chains <= 0) return fail(FCU_ERR_ARG, "bad sequence parameters");
+  if (!out || !HostState::seq_ok(sp)) return fail(FCU_ERR_ARG, "bad sequence parameters");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || sp->device >= ndev) return fail(FCU_ERR_NO_DEVICE, "no HIP device: libfcu has no CPU fallback");
   HIPCHK(hipSetDevice(sp->device));
   fcu_ctx *c = new fcu_ctx();
-  c->sp = *sp; c->n_ctu = ((sp->width + 63) / 64) * ((sp->height + 63) / 64);
-  c->ms_acc = 0; c->launches = 0;
-  c->d_chains = nullptr; c->d_scratch = nullptr; c->d_hist = nullptr; c->hist_cap = 0; c->d_thr = nullptr; c->thr_cap = 0; c->d_sao = nullptr; c->sao_cap = 0; c->d_rep = nullptr; c->rep_cap = 0;
-  c->d_wpp_ctl = nullptr; c->wpp_ctl_bytes = 0; c->d_wpp_sync = nullptr;
   struct Guard { fcu_ctx *c; ~Guard() { if (c) { hipFree(c->d_chains); hipFree(c->d_scratch); delete c; } } } guard{ c };   /* frees on every early return */
   HIPCHK(hipMalloc((void **)&c->d_chains, sizeof(Chain) * (size_t)sp->max_chains));
   HIPCHK(hipMalloc((void **)&c->d_scratch, sizeof(Scratch) * (size_t)sp->max_chains));
   HIPCHK(hipMemset(c->d_chains, 0, sizeof(Chain) * (size_t)sp->max_chains));
   guard.c = nullptr;
-  c->h_chains.resize((size_t)sp->max_chains);
-  memset(c->h_chains.data(), 0, sizeof(Chain) * (size_t)sp->max_chains);
-  c->h_pos.assign((size_t)sp->max_chains, 0);
+  c->hs.init(*sp);
   *out = c;
   return FCU_OK;
 }
@@ -176,29 +224,22 @@ int fcu_create(const fcu_seq_params *sp, fcu_ctx **out)
 void fcu_destroy(fcu_ctx *c)
 {
   if (!c) return;
-  hipSetDevice(c->sp.device);
+  hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->d_hist); hipFree(c->d_thr); hipFree(c->d_sao); hipFree(c->d_rep);
-  hipFree(c->d_wpp_ctl); hipFree(c->d_wpp_sync);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p);
+  hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
 
-int fcu_num_ctus(const fcu_ctx *c) { return c ? c->n_ctu : 0; }
+int fcu_num_ctus(const fcu_ctx *c) { return c ? c->hs.n_ctu : 0; }
 
 int fcu_chain_begin(fcu_ctx *c, int chain, const fcu_frame_params *fp,
                     const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (!c || !fp || chain < 0 || chain >= c->sp.max_chains || !oy || !ou || !ov || !ry || !ru || !rv || !dev_out) return fail(FCU_ERR_ARG, "fcu_chain_begin: bad argument");
-  if (fp->qp < 0 || fp->qp > 51 || fp->slice_ctus < 0) return fail(FCU_ERR_ARG, "fcu_chain_begin: QP / slice_ctus out of range");
-  if (fp->slice_type != FCU_SLICE_I && fp->slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, "fcu_chain_begin: unknown slice type");
-  if (fp->slice_type == FCU_SLICE_P && (!(fp->lambda > 0.0) || fp->search_range < 1 || fp->search_range > 64)) return fail(FCU_ERR_ARG, "fcu_chain_begin: a P slice needs its lambda (fcu_ldp_slice) and 1 <= search_range <= 64");
-  HIPCHK(hipSetDevice(c->sp.device));
-  Chain &h = c->h_chains[(size_t)chain];
-  chain_bind(h, c->sp.width, c->sp.height, *fp, oy, ou, ov, ry, ru, rv, dev_out);
-  c->h_pos[(size_t)chain] = 0;
-  HIPCHK(hipMemcpy(&c->d_chains[chain], &h, sizeof(Chain), hipMemcpyHostToDevice));
-  return FCU_OK;
+  HOST("fcu_chain_begin: bad argument", chain_begin(chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out }));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  return upload(c, chain, 1, CR_ALL, false);
 }
 
 void fcu_ldp_slice(fcu_frame_params *fp, int base_qp, int poc) { if (fp) ldp_slice(*fp, base_qp, poc); }
@@ -206,19 +247,19 @@ void fcu_ldp_slice(fcu_frame_params *fp, int base_qp, int poc) { if (fp) ldp_sli
 void fcu_pad_sizes(const fcu_ctx *c, size_t *out3)
 {
   if (!c || !out3) return;
-  out3[0] = (size_t)(c->sp.width + 2 * FCU_REF_MARGIN) * (size_t)(c->sp.height + 2 * FCU_REF_MARGIN);
-  out3[1] = out3[2] = (size_t)(c->sp.width / 2 + FCU_REF_MARGIN) * (size_t)(c->sp.height / 2 + FCU_REF_MARGIN);
+  out3[0] = (size_t)(c->hs.sp.width + 2 * FCU_REF_MARGIN) * (size_t)(c->hs.sp.height + 2 * FCU_REF_MARGIN);
+  out3[1] = out3[2] = (size_t)(c->hs.sp.width / 2 + FCU_REF_MARGIN) * (size_t)(c->hs.sp.height / 2 + FCU_REF_MARGIN);
 }
 int fcu_ldp_layer(int poc) { static const int layer[4] = { 0, 2, 1, 2 }; return poc < 0 ? 0 : layer[poc & 3]; }
 
 int fcu_pad_reference(fcu_ctx *c, const uint8_t *dy, const uint8_t *du, const uint8_t *dv, uint8_t *py, uint8_t *pu, uint8_t *pv, void *hip_stream)
 {
   if (!c || !dy || !du || !dv || !py || !pu || !pv) return fail(FCU_ERR_ARG, "fcu_pad_reference: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
   const uint8_t *src[3] = { dy, du, dv }; uint8_t *dst[3] = { py, pu, pv };
   for (int k = 0; k < 3; k++) {
-    const int w = k ? c->sp.width / 2 : c->sp.width, h = k ? c->sp.height / 2 : c->sp.height, m = k ? FCU_REF_MARGIN / 2 : FCU_REF_MARGIN;
+    const int w = k ? c->hs.sp.width / 2 : c->hs.sp.width, h = k ? c->hs.sp.height / 2 : c->hs.sp.height, m = k ? FCU_REF_MARGIN / 2 : FCU_REF_MARGIN;
     const int n = ((w + 2 * m + 15) >> 4) * (h + 2 * m);
     hipLaunchKernelGGL(fcu_pad_plane, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src[k], w, h, dst[k], m);
     HIPCHK(hipGetLastError());
@@ -228,180 +269,104 @@ int fcu_pad_reference(fcu_ctx *c, const uint8_t *dy, const uint8_t *du, const ui
 
 int fcu_chain_set_reference(fcu_ctx *c, int chain, const uint8_t *py, const uint8_t *pu, const uint8_t *pv)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !py || !pu || !pv) return fail(FCU_ERR_ARG, "fcu_chain_set_reference: bad argument");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_reference: chain not bound (fcu_chain_begin)");
-  HIPCHK(hipSetDevice(c->sp.device));
-  static_assert(offsetof(Chain, ref_stride) == offsetof(Chain, ref) + 3 * sizeof(void *), "ref / ref_stride are adjacent");
+  if (!c || !py || !pu || !pv) return fail(FCU_ERR_ARG, "fcu_chain_set_reference: bad argument");
+  HOST("", bound("fcu_chain_set_reference", chain));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   /* this entry point: one reference picture at POC distance 1 (no vector is ever scaled), list 0 = { this picture } */
   const uint8_t *const planes[3] = { py, pu, pv };
   const int ref_poc = 0;
-  chain_set_list0(h, 1, planes, &ref_poc, 1);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, ref), &h.ref[0], 3 * sizeof(void *) + 3 * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
-  return FCU_OK;
+  chain_set_list0(c->hs.chains[(size_t)chain], 1, planes, &ref_poc, 1);
+  CHK(upload(c, chain, 1, CR_REF, true));
+  return upload(c, chain, 1, CR_LIST0, false);
 }
 
 int fcu_chain_set_references(fcu_ctx *c, int chain, int n_ref, const uint8_t *const *dev_pad_planes, const int *ref_pocs, int cur_poc)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || n_ref < 1 || n_ref > FCU_MAX_REF || !dev_pad_planes || !ref_pocs) return fail(FCU_ERR_ARG, "fcu_chain_set_references: bad argument");
+  if (!c || !c->hs.has(chain) || n_ref < 1 || n_ref > FCU_MAX_REF || !dev_pad_planes || !ref_pocs) return fail(FCU_ERR_ARG, "fcu_chain_set_references: bad argument");
   for (int k = 0; k < 3 * n_ref; k++) if (!dev_pad_planes[k]) return fail(FCU_ERR_ARG, "fcu_chain_set_references: null plane");
   for (int a = 0; a < n_ref; a++) { if (ref_pocs[a] == cur_poc) return fail(FCU_ERR_ARG, "fcu_chain_set_references: a reference picture cannot have the current POC");
     for (int b = 0; b < a; b++) if (ref_pocs[a] == ref_pocs[b]) return fail(FCU_ERR_ARG, "fcu_chain_set_references: the same picture twice in the list"); }
-  int rc = fcu_chain_set_reference(c, chain, dev_pad_planes[0], dev_pad_planes[1], dev_pad_planes[2]);
-  if (rc != FCU_OK) return rc;
-  Chain &h = c->h_chains[(size_t)chain];
-  chain_set_list0(h, n_ref, dev_pad_planes, ref_pocs, cur_poc);       /* (ref / ref_stride: the values the call above has copied) */
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
-  return FCU_OK;
+  CHK(fcu_chain_set_reference(c, chain, dev_pad_planes[0], dev_pad_planes[1], dev_pad_planes[2]));
+  chain_set_list0(c->hs.chains[(size_t)chain], n_ref, dev_pad_planes, ref_pocs, cur_poc);       /* (ref / ref_stride: the values the call above has copied) */
+  return upload(c, chain, 1, CR_LIST0, false);
 }
 
 int fcu_chain_get_search_state(fcu_ctx *c, int chain, int32_t *xy)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !xy) return fail(FCU_ERR_ARG, "fcu_chain_get_search_state: bad argument");
-  static_assert(sizeof(((Chain *)0)->int_mv_r) == 2 * FCU_MAX_REF * sizeof(int32_t), "search state layout");
-  HIPCHK(hipSetDevice(c->sp.device));
+  if (!c || !c->hs.has(chain) || !xy) return fail(FCU_ERR_ARG, "fcu_chain_get_search_state: bad argument");
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(xy, (const char *)&c->d_chains[chain] + offsetof(Chain, int_mv_r), 2 * FCU_MAX_REF * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(xy, (const char *)&c->d_chains[chain] + CR_INT_MV.off, CR_INT_MV.len, hipMemcpyDeviceToHost));
   return FCU_OK;
 }
 int fcu_chain_set_search_state(fcu_ctx *c, int chain, const int32_t *xy)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !xy) return fail(FCU_ERR_ARG, "fcu_chain_set_search_state: bad argument");
-  if (c->h_chains[(size_t)chain].out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_search_state: chain not bound (fcu_chain_begin)");
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, int_mv_r), xy, 2 * FCU_MAX_REF * sizeof(int32_t), hipMemcpyHostToDevice));
-  return FCU_OK;
+  if (!c || !xy) return fail(FCU_ERR_ARG, "fcu_chain_set_search_state: bad argument");
+  HOST("", bound("fcu_chain_set_search_state", chain));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  return upload(c, chain, 1, CR_INT_MV, true, xy);          /* the device copy alone: the host descriptor keeps its own */
 }
 
 int fcu_chain_set_collocated_pocs(fcu_ctx *c, int chain, int col_poc, const int *col_ref_pocs, int n)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !col_ref_pocs || n < 1 || n > FCU_MAX_REF) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: bad argument");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_collocated_pocs: chain not bound (fcu_chain_begin)");
-  HIPCHK(hipSetDevice(c->sp.device));
-  if (!chain_set_collocated_pocs(h, col_poc, col_ref_pocs, n)) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: a reference of the collocated picture has its own POC");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, refs), (const char *)&h + offsetof(Chain, refs), offsetof(Chain, int_mv_r) - offsetof(Chain, refs), hipMemcpyHostToDevice));
-  return FCU_OK;
+  if (!c || !col_ref_pocs || n < 1 || n > FCU_MAX_REF) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: bad argument");
+  HOST("", bound("fcu_chain_set_collocated_pocs", chain));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  if (!chain_set_collocated_pocs(c->hs.chains[(size_t)chain], col_poc, col_ref_pocs, n)) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated_pocs: a reference of the collocated picture has its own POC");
+  return upload(c, chain, 1, CR_LIST0, true);
 }
 
 int fcu_chain_set_range(fcu_ctx *c, int chain, int first_ctu, int n_ctus)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_chain_set_range: bad argument");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_range: chain not bound (fcu_chain_begin)");
-  if (h.wpp) return fail(FCU_ERR_STATE, "fcu_chain_set_range: a WaveFrontSynchro row chain keeps the row fcu_wpp_begin gave it");
-  if (!tile_is_picture(h)) return fail(FCU_ERR_STATE, "fcu_chain_set_range: a tile chain keeps the tile fcu_tiles_begin gave it");
-  const int sl = h.p.slice_ctus;
-  if (first_ctu < 0 || n_ctus <= 0 || first_ctu + n_ctus > h.n_ctu) return fail(FCU_ERR_ARG, "fcu_chain_set_range: range outside the frame");
-  /* a chain may only start where the reference resets its entropy coder and cuts the neighbourhood: at a slice start */
-  if (first_ctu != 0 && (sl <= 0 || first_ctu % sl != 0)) return fail(FCU_ERR_ARG, "fcu_chain_set_range: a chain must start at a slice boundary");
-  if (first_ctu + n_ctus != h.n_ctu && (sl <= 0 || (first_ctu + n_ctus) % sl != 0)) return fail(FCU_ERR_ARG, "fcu_chain_set_range: a chain must end at a slice boundary");
-  HIPCHK(hipSetDevice(c->sp.device));
-  h.next_ctu = first_ctu; h.end_ctu = first_ctu + n_ctus;
-  c->h_pos[(size_t)chain] = first_ctu;
+  HOST("fcu_chain_set_range: bad argument", set_range(chain, first_ctu, n_ctus));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   /* only the range: the chain's coder state, verification counters and trial count on the device stay as they are */
-  static_assert(offsetof(Chain, end_ctu) == offsetof(Chain, next_ctu) + sizeof(int), "next_ctu / end_ctu are adjacent");
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, next_ctu), &h.next_ctu, 2 * sizeof(int), hipMemcpyHostToDevice));
-  return FCU_OK;
+  return upload(c, chain, 1, CR_RANGE, true);
 }
 
 int fcu_compress_chains(fcu_ctx *c, int first, int n, int ctus, void *hip_stream)
 {
-  if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains || ctus <= 0) return fail(FCU_ERR_ARG, "fcu_compress_chains: bad range");
-  for (int i = first; i < first + n; i++) {
-    if (c->h_chains[(size_t)i].out == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_chains: chain not bound (fcu_chain_begin)");
-    if (c->h_chains[(size_t)i].wpp) return fail(FCU_ERR_STATE, "fcu_compress_chains: a WaveFrontSynchro row chain is decided by fcu_compress_wpp");
-    if (c->h_chains[(size_t)i].p.slice_type == SLICE_P && c->h_chains[(size_t)i].ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_chains: P chain without reference picture (fcu_chain_set_reference)");
-  }
-  HIPCHK(hipSetDevice(c->sp.device));
+  HOST("fcu_compress_chains: bad range", chains_check(first, n, ctus));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(fcu_ctu_engine, dim3((unsigned)n), dim3(64), 0, st, c->d_chains, c->d_scratch, first, ctus);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, st));
-  c->ev.push_back(e0); c->ev.push_back(e1);
-  harvest_events(c, FCU_MAX_PENDING_EVENTS);
-  for (int i = first; i < first + n; i++) { int &p = c->h_pos[(size_t)i]; p += ctus; if (p > c->h_chains[(size_t)i].end_ctu) p = c->h_chains[(size_t)i].end_ctu; }
+  CHK(timed_launch(c, st, [&] { hipLaunchKernelGGL(fcu_ctu_engine, dim3((unsigned)n), dim3(64), 0, st, c->d_chains, c->d_scratch, first, ctus); }));
+  c->hs.chains_launched(first, n, ctus);
   return FCU_OK;
 }
 
-int fcu_wpp_rows(const fcu_ctx *c) { return c ? (c->sp.height + 63) / 64 : 0; }
+int fcu_wpp_rows(const fcu_ctx *c) { return c ? c->hs.h_ctu : 0; }
 
-/* the control words and sync slots of WaveFrontSynchro launches, allocated by the first binder that needs them */
-static int wpp_alloc(fcu_ctx *c, const char *name)
+/* the five picture entry points: the binder's checks (HostState::picture_check), the WaveFrontSynchro blocks where rows are
+ * chains, the descriptors of the picture's chains (HostState::picture_bind), one copy to the device */
+static int picture_begin(fcu_ctx *c, const PictureCut &cut, int first_chain, const fcu_frame_params *fp, const Planes &pl)
 {
-  if (c->d_wpp_ctl) return FCU_OK;
-  const size_t ctl = ((size_t)(WPP_CTL_WORDS + c->sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15;
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipMalloc((void **)&c->d_wpp_ctl, ctl));
-  if (hipMalloc((void **)&c->d_wpp_sync, (size_t)WPP_SYNC_BYTES * c->sp.max_chains) != hipSuccess) {
-    hipFree(c->d_wpp_ctl); c->d_wpp_ctl = nullptr; return fail(FCU_ERR_HIP, std::string(name) + ": out of device memory");
+  if (!c) return fail(FCU_ERR_ARG, std::string(cut.name) + ": bad argument");
+  { const int rc = c->hs.picture_check(cut, first_chain, fp, pl); if (rc != FCU_OK) return fail(rc, c->hs.err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  if (cut.wpp) {                                             /* the control words and sync slots: sized once, so allocated once */
+    HIPCHK(c->wpp_ctl.reserve(((size_t)(WPP_CTL_WORDS + c->hs.sp.max_chains) * sizeof(unsigned) + 15) & ~(size_t)15, nullptr));
+    HIPCHK(c->wpp_sync.reserve((size_t)WPP_SYNC_BYTES * c->hs.sp.max_chains, nullptr));
   }
-  c->wpp_ctl_bytes = ctl;
-  return FCU_OK;
-}
-
-/* the binding the WPP entry points share: `name` for the messages, the slice type already checked by the caller.  slice_rows
- * 0 = a one-slice picture (fp->slice_ctus must be 0); slice_rows R >= 1 (fcu_wpp_begin_slices) = slices of R whole CTU rows.
- * A row that starts a slice is bound as a row 0 is: no row above (wpp_above -1) and no sync slot to read, so run_wpp_chain
- * waits for nothing and inherits nothing on it, and compress_ctu resets its coder as the first CTU of a slice (fcu_host.h). */
-static int wpp_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp_in, const char *name, int slice_rows,
-                    const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
-{
-  const int rows = fcu_wpp_rows(c), W = (c->sp.width + 63) / 64;
-  fcu_frame_params fp_sliced = *fp_in;
-  const fcu_frame_params *fp = fp_in;
-  if (slice_rows == 0) {
-    if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": WaveFrontSynchro needs one slice per picture (slice_ctus 0); slices of whole CTU rows are bound by fcu_wpp_begin_slices");
-  } else {
-    const int sl = wpp_slice_ctus(W, slice_rows, fp->slice_ctus);
-    if (sl < 0) return fail(FCU_ERR_ARG, std::string(name) + ": slice_rows must be >= 1 and slice_ctus 0 or slice_rows x the picture width in CTUs (a slice starts at a row start)");
-    fp_sliced.slice_ctus = sl; fp = &fp_sliced;
-  }
-  if (first_chain < 0 || first_chain + rows > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains for one chain per CTU row (fcu_wpp_rows)");
-  { const int rc = wpp_alloc(c, name); if (rc != FCU_OK) return rc; }
-  const int rc = fcu_chain_begin(c, first_chain, fp, oy, ou, ov, ry, ru, rv, dev_out);     /* checks the rest, fills the row-0 descriptor */
-  if (rc != FCU_OK) return rc;
-  const Chain base = c->h_chains[(size_t)first_chain];
-  for (int r = 0; r < rows; r++) {
-    Chain &h = c->h_chains[(size_t)(first_chain + r)];
-    h = base;
-    wpp_bind_row(h, r, W, slice_rows, first_chain, c->d_wpp_sync);
-    c->h_pos[(size_t)(first_chain + r)] = r * W;
-  }
-  HIPCHK(hipMemcpy(&c->d_chains[first_chain], &c->h_chains[(size_t)first_chain], sizeof(Chain) * (size_t)rows, hipMemcpyHostToDevice));
-  return FCU_OK;
+  const int n = c->hs.picture_bind(cut, first_chain, *fp, pl, (uint8_t *)c->wpp_sync.p);
+  return upload(c, first_chain, n, CR_ALL, false);
 }
 
 int fcu_wpp_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
                   const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin: bad argument");
-  if (fp->slice_type != FCU_SLICE_I) return fail(FCU_ERR_ARG, "fcu_wpp_begin: binds I slices only (P slices: fcu_wpp_begin_p)");
-  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin", 0, oy, ou, ov, ry, ru, rv, dev_out);
+  return picture_begin(c, PictureCut::rows(FCU_SLICE_I), first_chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out });
 }
 
 int fcu_wpp_begin_p(fcu_ctx *c, int first_chain, const fcu_frame_params *fp,
                     const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: bad argument");
-  if (fp->slice_type != FCU_SLICE_P) return fail(FCU_ERR_ARG, "fcu_wpp_begin_p: binds P slices only (I slices: fcu_wpp_begin)");
-  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_p", 0, oy, ou, ov, ry, ru, rv, dev_out);
+  return picture_begin(c, PictureCut::rows(FCU_SLICE_P), first_chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out });
 }
 
 int fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int slice_rows,
                          const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  if (!c || !fp) return fail(FCU_ERR_ARG, "fcu_wpp_begin_slices: bad argument");
-  if (slice_rows < 1) return fail(FCU_ERR_ARG, "fcu_wpp_begin_slices: slice_rows must be at least 1");
-  return wpp_bind(c, first_chain, fp, "fcu_wpp_begin_slices", slice_rows, oy, ou, ov, ry, ru, rv, dev_out);     /* the slice type: fcu_chain_begin's check */
+  return picture_begin(c, PictureCut::row_slices(slice_rows), first_chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out });     /* the slice type: fcu_chain_begin's check */
 }
 
 /* ---- tiles of a one-slice picture */
@@ -411,130 +376,40 @@ int fcu_tile_grid(int width_in_ctus, int height_in_ctus, int n_cols, int n_rows,
   return FCU_OK;
 }
 
-int fcu_tile_chains(const fcu_ctx *c, int n_cols, int n_rows, int wpp)
-{
-  return c ? tile_chains((c->sp.width + 63) / 64, (c->sp.height + 63) / 64, n_cols, n_rows, wpp) : -1;
-}
-
-/* the binding fcu_tiles_begin and fcu_wpp_begin_tiles share: chain_bind (through fcu_chain_begin, which checks the frame
- * parameters) for the first chain, then every tile in tile-scan order through tile_bind, and with wpp every CTU row of the tile
- * through wpp_bind_tile_row */
-static int tiles_bind(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows, int wpp, const char *name,
-                      const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
-{
-  if (!c || !fp) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
-  const int W = (c->sp.width + 63) / 64, H = (c->sp.height + 63) / 64;
-  std::vector<int> cb((size_t)(n_cols > 0 ? n_cols : 0) + 1), rb((size_t)(n_rows > 0 ? n_rows : 0) + 1);
-  if (!tile_grid(W, H, n_cols, n_rows, cb.data(), rb.data())) return fail(FCU_ERR_ARG, std::string(name) + ": a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
-  if (fp->slice_ctus != 0) return fail(FCU_ERR_ARG, std::string(name) + ": tiles need one slice per picture (slice_ctus 0)");
-  if (!tile_params_ok(*fp, n_cols)) return fail(FCU_ERR_ARG, std::string(name) + ": TMVP across tile columns is not supported (tmvp 1 needs n_cols 1)");
-  const int n = tile_chains(W, H, n_cols, n_rows, wpp);
-  if (first_chain < 0 || first_chain + n > c->sp.max_chains) return fail(FCU_ERR_ARG, std::string(name) + ": too few chains (fcu_tile_chains)");
-  if (wpp) { const int rc = wpp_alloc(c, name); if (rc != FCU_OK) return rc; }
-  const int rc = fcu_chain_begin(c, first_chain, fp, oy, ou, ov, ry, ru, rv, dev_out);
-  if (rc != FCU_OK) return rc;
-  const Chain base = c->h_chains[(size_t)first_chain];
-  int i = first_chain;
-  for (int ty = 0; ty < n_rows; ty++) for (int tx = 0; tx < n_cols; tx++) {
-    const int x0 = cb[(size_t)tx], y0 = rb[(size_t)ty], tw = cb[(size_t)tx + 1] - x0, th = rb[(size_t)ty + 1] - y0;
-    for (int r = 0; r < (wpp ? th : 1); r++, i++) {
-      Chain &h = c->h_chains[(size_t)i];
-      h = base;
-      tile_bind(h, x0, y0, tw, th);
-      if (wpp) wpp_bind_tile_row(h, r, i, c->d_wpp_sync);
-      c->h_pos[(size_t)i] = h.next_ctu;
-    }
-  }
-  HIPCHK(hipMemcpy(&c->d_chains[first_chain], &c->h_chains[(size_t)first_chain], sizeof(Chain) * (size_t)n, hipMemcpyHostToDevice));
-  return FCU_OK;
-}
+int fcu_tile_chains(const fcu_ctx *c, int n_cols, int n_rows, int wpp) { return c ? c->hs.picture_chains(PictureCut::tiles(n_cols, n_rows, wpp)) : -1; }
 
 int fcu_tiles_begin(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
                     const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  return tiles_bind(c, first_chain, fp, n_cols, n_rows, 0, "fcu_tiles_begin", oy, ou, ov, ry, ru, rv, dev_out);
+  return picture_begin(c, PictureCut::tiles(n_cols, n_rows, 0), first_chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out });
 }
 
 int fcu_wpp_begin_tiles(fcu_ctx *c, int first_chain, const fcu_frame_params *fp, int n_cols, int n_rows,
                         const uint8_t *oy, const uint8_t *ou, const uint8_t *ov, uint8_t *ry, uint8_t *ru, uint8_t *rv, fcu_ctu_out *dev_out)
 {
-  return tiles_bind(c, first_chain, fp, n_cols, n_rows, 1, "fcu_wpp_begin_tiles", oy, ou, ov, ry, ru, rv, dev_out);
-}
-
-/* the rows of a P picture decide one picture: every row must name row 0's reference pictures and collocated field */
-static bool wpp_same_refs(const Chain &a, const Chain &b)
-{
-  if (a.n_ref != b.n_ref || a.poc != b.poc || a.col != b.col || a.col_poc != b.col_poc || a.ref_stride[0] != b.ref_stride[0]) return false;
-  for (int k = 0; k < 3; k++) if (a.ref[k] != b.ref[k]) return false;
-  for (int r = 0; r < FCU_MAX_REF; r++) {
-    if (a.col_ref_poc[r] != b.col_ref_poc[r]) return false;
-    if (r >= a.n_ref) continue;
-    if (a.ref_poc[r] != b.ref_poc[r]) return false;
-    for (int k = 0; k < 3; k++) if (a.refs[r][k] != b.refs[r][k]) return false;
-  }
-  return true;
+  return picture_begin(c, PictureCut::tiles(n_cols, n_rows, 1), first_chain, fp, Planes{ oy, ou, ov, ry, ru, rv, dev_out });
 }
 
 int fcu_compress_wpp(fcu_ctx *c, int first, int n, void *hip_stream)
 {
-  if (!c || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_compress_wpp: bad range");
-  int pic0 = first;                                         /* first chain of the picture chain i belongs to */
-  for (int i = first; i < first + n; i++) {
-    const Chain &h = c->h_chains[(size_t)i];
-    if (h.out == nullptr || !h.wpp) return fail(FCU_ERR_STATE, "fcu_compress_wpp: chain not bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles");
-    /* a picture starts with its row 0 (at `first` or right after the last row of the picture before it) and its rows follow at
-     * consecutive chains; a row without a row above that is not row 0 must be the first row of a slice of whole rows of the
-     * picture the chain before it belongs to (fcu_wpp_begin_slices) */
-    /* with tiles (fcu_wpp_begin_tiles; slice_ctus 0) "row" is the row inside the chain's tile and positions count inside it: the
-     * tiles of a picture follow each other in tile-scan order, each with its rows at consecutive chains, and a picture ends with
-     * the last row of its last tile.  Without tiles the tile is the picture and the rules read as before. */
-    const int row = h.next_ctu / h.tile_w, slice_rows = h.p.slice_ctus / h.w_ctu;      /* slice_ctus 0 = one slice: slice_rows 0, every row below row 0 has a row above */
-    const Chain *b = i > first ? &c->h_chains[(size_t)i - 1] : nullptr;
-    const bool b_ends_tile = b && b->end_ctu == b->tile_w * b->tile_h;
-    bool starts_ok;
-    if (row == 0 && h.tile_x0 == 0 && h.tile_y0 == 0) { starts_ok = h.wpp_above < 0 && (i == first || (b_ends_tile && tile_is_last(*b))); pic0 = i; }
-    else if (row == 0) {                                    /* the tile after b's in tile-scan order: to its right, or the first of the next tile row */
-      const bool b_row_end = b && b->tile_x0 + b->tile_w == b->w_ctu;
-      starts_ok = h.wpp_above < 0 && b_ends_tile && b->out == h.out &&
-                  (b_row_end ? h.tile_x0 == 0 && h.tile_y0 == b->tile_y0 + b->tile_h : h.tile_x0 == b->tile_x0 + b->tile_w && h.tile_y0 == b->tile_y0);
-    }
-    else {
-      const int ra = wpp_row_above(row, slice_rows);
-      starts_ok = b && b->out == h.out && b->end_ctu == h.next_ctu && b->p.slice_ctus == h.p.slice_ctus && h.wpp_above == (ra >= 0 ? i - 1 : -1)
-                  && b->tile_x0 == h.tile_x0 && b->tile_y0 == h.tile_y0 && b->tile_w == h.tile_w && b->tile_h == h.tile_h;
-    }
-    if (!starts_ok) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must hold whole pictures bound by fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles, their rows at consecutive chains (tiles: in tile-scan order, the rows of a tile top to bottom)");
-    if (i == first + n - 1 && !(h.end_ctu == h.tile_w * h.tile_h && tile_is_last(h))) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the range must end with the last row of a picture (tiles: of its last tile)");
-    if (c->h_pos[(size_t)i] != h.next_ctu) return fail(FCU_ERR_STATE, "fcu_compress_wpp: picture already decided (bind it again with fcu_wpp_begin(_p) / fcu_wpp_begin_slices / fcu_wpp_begin_tiles)");
-    if (h.p.slice_type == SLICE_P) {
-      if (h.ref[0] == nullptr) return fail(FCU_ERR_STATE, "fcu_compress_wpp: P row without reference picture (fcu_chain_set_reference(s) on every row)");
-      const Chain &row0 = c->h_chains[(size_t)pic0];
-      if (!wpp_same_refs(h, row0)) return fail(FCU_ERR_STATE, "fcu_compress_wpp: the rows of a P picture name different reference pictures or collocated fields");
-    }
-  }
-  HIPCHK(hipSetDevice(c->sp.device));
+  HOST("fcu_compress_wpp: bad range", wpp_check(first, n));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipMemsetAsync(c->d_wpp_ctl, 0, c->wpp_ctl_bytes, st));          /* ticket, abort and progress words: every launch */
-  HIPCHK(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(fcu_ctu_engine_wpp, dim3((unsigned)n), dim3(64), 0, st, c->d_chains, c->d_scratch, c->d_wpp_ctl, first);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, st));
-  c->ev.push_back(e0); c->ev.push_back(e1);
-  harvest_events(c, FCU_MAX_PENDING_EVENTS);
+  unsigned *ctl = (unsigned *)c->wpp_ctl.p;
+  HIPCHK(hipMemsetAsync(ctl, 0, c->wpp_ctl.cap, st));          /* ticket, abort and progress words: every launch */
+  CHK(timed_launch(c, st, [&] { hipLaunchKernelGGL(fcu_ctu_engine_wpp, dim3((unsigned)n), dim3(64), 0, st, c->d_chains, c->d_scratch, ctl, first); }));
   unsigned abort_word = 0;
   HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipMemcpy(&abort_word, c->d_wpp_ctl + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&abort_word, ctl + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
   if (abort_word) return fail(FCU_ERR_STATE, "fcu_compress_wpp: a row waited for the row above beyond the give-up time; the launch was abandoned");
-  for (int i = first; i < first + n; i++) c->h_pos[(size_t)i] = c->h_chains[(size_t)i].end_ctu;
+  c->hs.wpp_launched(first, n);
   return FCU_OK;
 }
 
 int fcu_sync(fcu_ctx *c)
 {
   if (!c) return fail(FCU_ERR_ARG, "null ctx");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   HIPCHK(hipDeviceSynchronize());
   return FCU_OK;
 }
@@ -542,7 +417,7 @@ int fcu_sync(fcu_ctx *c)
 double fcu_kernel_ms(fcu_ctx *c, int *launches)
 {
   if (!c) return 0.0;
-  hipSetDevice(c->sp.device);
+  hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   harvest_events(c, 0);
   const int n = c->launches; const double avg = n ? c->ms_acc / n : 0.0;
@@ -551,109 +426,77 @@ double fcu_kernel_ms(fcu_ctx *c, int *launches)
   return avg;
 }
 
-int fcu_chain_position(fcu_ctx *c, int chain)
-{
-  if (!c || chain < 0 || chain >= c->sp.max_chains) return -1;
-  return c->h_pos[(size_t)chain];
-}
+int fcu_chain_position(fcu_ctx *c, int chain) { return c ? c->hs.position(chain) : -1; }
 
 int fcu_compress_ctu(fcu_ctx *c, int chain, uint32_t ctuRsAddr, fcu_ctu_out *host_out)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !host_out) return fail(FCU_ERR_ARG, "fcu_compress_ctu: bad argument");
-  /* (a tile chain's position counts CTUs inside its tile; the CTU is still named by its picture address) */
-  if (c->h_pos[(size_t)chain] >= c->h_chains[(size_t)chain].end_ctu || c->h_chains[(size_t)chain].out == nullptr || (int)ctuRsAddr != tile_ctu_addr(c->h_chains[(size_t)chain], c->h_pos[(size_t)chain])) return fail(FCU_ERR_STATE, "fcu_compress_ctu: CTUs of a chain must be decided in raster order");
-  int r = fcu_compress_chains(c, chain, 1, 1, nullptr);
-  if (r != FCU_OK) return r;
+  if (!c || !host_out) return fail(FCU_ERR_ARG, "fcu_compress_ctu: bad argument");
+  HOST("", ctu_check(chain, ctuRsAddr));
+  CHK(fcu_compress_chains(c, chain, 1, 1, nullptr));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host_out, c->h_chains[(size_t)chain].out + ctuRsAddr, sizeof(fcu_ctu_out), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host_out, c->hs.chains[(size_t)chain].out + ctuRsAddr, sizeof(fcu_ctu_out), hipMemcpyDeviceToHost));
   return FCU_OK;
 }
 
 /* diagnostic: per-chain section timers (only meaningful in a -DFCU_PROFILE build) and TU-trial count */
 int fcu_debug_counters(fcu_ctx *c, int chain, unsigned long long *out17)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !out17) return fail(FCU_ERR_ARG, "fcu_debug_counters: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipDeviceSynchronize());
-  Chain h;
-  HIPCHK(hipMemcpy(&h, &c->d_chains[chain], sizeof(Chain), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 16; i++) out17[i] = h.prof[i];
-  out17[16] = h.n_tu_trials;
+  if (!c || !c->hs.has(chain) || !out17) return fail(FCU_ERR_ARG, "fcu_debug_counters: bad argument");
+  std::vector<Chain> h;
+  CHK(read_back(c, chain, 1, h));
+  for (int i = 0; i < 16; i++) out17[i] = h[0].prof[i];
+  out17[16] = h[0].n_tu_trials;
   return FCU_OK;
 }
 
-int fcu_get_ctx_state(fcu_ctx *c, int chain, uint8_t *ctx160, uint64_t *frac_bits)
+/* the coder state a chain stands at: n_ctx = NCTX_INTRA (fcu_get_ctx_state) or NCTX (fcu_get_ctx_state_full) context bytes */
+static int get_ctx_state(fcu_ctx *c, int chain, uint8_t *ctx, int n_ctx, uint64_t *frac_bits, const char *name)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !ctx160 || !frac_bits) return fail(FCU_ERR_ARG, "fcu_get_ctx_state: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipDeviceSynchronize());
-  Chain h;
-  HIPCHK(hipMemcpy(&h, &c->d_chains[chain], sizeof(Chain), hipMemcpyDeviceToHost));
-  memcpy(ctx160, h.state.ctx, NCTX_INTRA);
-  *frac_bits = h.state.frac;
+  if (!c || !c->hs.has(chain) || !ctx || !frac_bits) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
+  std::vector<Chain> h;
+  CHK(read_back(c, chain, 1, h));
+  memcpy(ctx, h[0].state.ctx, (size_t)n_ctx);
+  *frac_bits = h[0].state.frac;
   return FCU_OK;
 }
-
-int fcu_get_ctx_state_full(fcu_ctx *c, int chain, uint8_t *ctx176, uint64_t *frac_bits)
-{
-  if (!c || chain < 0 || chain >= c->sp.max_chains || !ctx176 || !frac_bits) return fail(FCU_ERR_ARG, "fcu_get_ctx_state_full: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipDeviceSynchronize());
-  Chain h;
-  HIPCHK(hipMemcpy(&h, &c->d_chains[chain], sizeof(Chain), hipMemcpyDeviceToHost));
-  memcpy(ctx176, h.state.ctx, NCTX);
-  *frac_bits = h.state.frac;
-  return FCU_OK;
-}
+int fcu_get_ctx_state(fcu_ctx *c, int chain, uint8_t *ctx160, uint64_t *frac_bits) { return get_ctx_state(c, chain, ctx160, NCTX_INTRA, frac_bits, "fcu_get_ctx_state"); }
+int fcu_get_ctx_state_full(fcu_ctx *c, int chain, uint8_t *ctx176, uint64_t *frac_bits) { return get_ctx_state(c, chain, ctx176, NCTX, frac_bits, "fcu_get_ctx_state_full"); }
 
 int fcu_chain_set_decision(fcu_ctx *c, int chain, const fcu_decision_params *dp)
 {
-  if (!c || !dp || chain < 0 || chain >= c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: bad argument");
+  if (!c || !dp || !c->hs.has(chain)) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: bad argument");
   if (dp->state < FCU_TRAINING || dp->state > FCU_TESTING) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: unknown state");
   if (dp->state != FCU_TRAINING && !dp->dev_obf) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: Verifying / Testing need the frame's OBF map (fcu_obf_prepass)");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_decision: chain not bound (fcu_chain_begin)");
-  HIPCHK(hipSetDevice(c->sp.device));
-  chain_set_decision(h, dp->state, dp->depth_exception, dp->dev_obf, dp->sw_skip2nx2n, dp->sw_terminate);
+  HOST("", bound("fcu_chain_set_decision", chain));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  chain_set_decision(c->hs.chains[(size_t)chain], dp->state, dp->depth_exception, dp->dev_obf, dp->sw_skip2nx2n, dp->sw_terminate);
   /* only the decision block of the descriptor: the chain's position and context state on the device stay as they are */
-  const size_t off = offsetof(Chain, dec_state);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + off, (const char *)&h + off, sizeof(Chain) - off, hipMemcpyHostToDevice));
-  return FCU_OK;
+  return upload(c, chain, 1, CR_DECISION, true);
 }
 
 int fcu_chain_set_collocated(fcu_ctx *c, int chain, const fcu_ctu_out *dev_col_out)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated: bad argument");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_collocated: chain not bound (fcu_chain_begin)");
+  HOST("fcu_chain_set_collocated: bad argument", bound("fcu_chain_set_collocated", chain));
+  Chain &h = c->hs.chains[(size_t)chain];
   if (dev_col_out == h.out) return fail(FCU_ERR_ARG, "fcu_chain_set_collocated: the collocated picture's array is the chain's own output array");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   h.col = dev_col_out;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, col), &h.col, sizeof(h.col), hipMemcpyHostToDevice));
-  return FCU_OK;
+  return upload(c, chain, 1, CR_COL, true);
 }
 int fcu_pu_index(int depth, int nxn, int zidx) { return nxn ? 85 + zidx : (depth <= 0 ? 0 : depth == 1 ? 1 + (zidx >> 6) : depth == 2 ? 5 + (zidx >> 4) : 21 + (zidx >> 2)); }
 int fcu_chain_set_pu_trace(fcu_ctx *c, int chain, fcu_pu_trace *dev_trace)
 {
-  if (!c || chain < 0 || chain >= c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_chain_set_pu_trace: bad argument");
-  Chain &h = c->h_chains[(size_t)chain];
-  if (h.out == nullptr) return fail(FCU_ERR_STATE, "fcu_chain_set_pu_trace: chain not bound (fcu_chain_begin)");
-  HIPCHK(hipSetDevice(c->sp.device));
-  h.pu_trace = dev_trace;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy((char *)&c->d_chains[chain] + offsetof(Chain, pu_trace), &h.pu_trace, sizeof(h.pu_trace), hipMemcpyHostToDevice));
-  return FCU_OK;
+  HOST("fcu_chain_set_pu_trace: bad argument", bound("fcu_chain_set_pu_trace", chain));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  c->hs.chains[(size_t)chain].pu_trace = dev_trace;
+  return upload(c, chain, 1, CR_PU_TRACE, true);
 }
 
 int fcu_get_verify_counts(fcu_ctx *c, int first, int n, fcu_verify_counts *host_sum)
 {
-  if (!c || !host_sum || first < 0 || n <= 0 || first + n > c->sp.max_chains) return fail(FCU_ERR_ARG, "fcu_get_verify_counts: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
-  HIPCHK(hipDeviceSynchronize());
-  std::vector<Chain> h((size_t)n);
-  HIPCHK(hipMemcpy(h.data(), &c->d_chains[first], sizeof(Chain) * (size_t)n, hipMemcpyDeviceToHost));
+  if (!c || !host_sum || first < 0 || n <= 0 || first + n > c->hs.sp.max_chains) return fail(FCU_ERR_ARG, "fcu_get_verify_counts: bad argument");
+  std::vector<Chain> h;
+  CHK(read_back(c, first, n, h));
   memset(host_sum, 0, sizeof(*host_sum));
   for (int i = 0; i < n; i++) for (int d = 0; d < 4; d++) for (int k = 0; k < 6; k++) host_sum->n[d][k] += h[(size_t)i].ver[d][k];
   return FCU_OK;
@@ -698,24 +541,23 @@ double fcu_tcm_threshold(const unsigned *hist, int hist_len, int n_samples)
 int fcu_obf_prepass(fcu_ctx *c, int n_frames, const uint8_t *dev_y, int16_t *dev_obf, double *host_yc, float *kernel_ms2, void *hip_stream)
 {
   if (!c || n_frames <= 0 || !dev_y || !dev_obf) return fail(FCU_ERR_ARG, "fcu_obf_prepass: bad argument");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  const int w = c->sp.width, h = c->sp.height, nblk = (w / 4) * (h / 4);
+  const int w = c->hs.sp.width, h = c->hs.sp.height, nblk = (w / 4) * (h / 4);
   const size_t frame_bytes = (size_t)w * h, hist_n = (size_t)n_frames * 15 * OBF_HB;
   /* histogram / threshold buffers belong to the context and only grow: no allocation in the steady state */
-  if (c->hist_cap < hist_n) { hipFree(c->d_hist); c->d_hist = nullptr; c->hist_cap = 0; HIPCHK(hipMalloc((void **)&c->d_hist, hist_n * sizeof(unsigned))); c->hist_cap = hist_n; }
-  if (c->thr_cap < (size_t)n_frames * 16) { hipFree(c->d_thr); c->d_thr = nullptr; c->thr_cap = 0; HIPCHK(hipMalloc((void **)&c->d_thr, (size_t)n_frames * 16 * sizeof(int))); c->thr_cap = (size_t)n_frames * 16; }
-  unsigned *d_hist = c->d_hist; int *d_thr = c->d_thr;
+  HIPCHK(c->hist.reserve(hist_n * sizeof(unsigned), st));
+  HIPCHK(c->thr.reserve((size_t)n_frames * 16 * sizeof(int), st));
+  unsigned *d_hist = (unsigned *)c->hist.p; int *d_thr = (int *)c->thr.p;
   HIPCHK(hipMemsetAsync(d_hist, 0, hist_n * sizeof(unsigned), st));
-  hipEvent_t e[4] = { nullptr, nullptr, nullptr, nullptr };
-  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 4; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
-  for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&e[i]));
+  Events ev(st, true);                                         /* (this call syncs with the host anyway: always timed) */
+  HIPCHK(ev.create(4));
   const int ngrp = (((w / 4) + 3) / 4) * (h / 4);               /* groups of four blocks along a row */
   const dim3 grid((unsigned)((ngrp + OBF_THREADS * OBF_GROUPS_PER_THREAD - 1) / (OBF_THREADS * OBF_GROUPS_PER_THREAD)), (unsigned)n_frames);
-  HIPCHK(hipEventRecord(e[0], st));
+  HIPCHK(ev.record(0));
   hipLaunchKernelGGL(obf_hist, grid, dim3(OBF_THREADS), 0, st, dev_y, w, h, frame_bytes, d_hist);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e[1], st));
+  HIPCHK(ev.record(1));
   std::vector<unsigned> hist(hist_n);
   HIPCHK(hipMemcpyAsync(hist.data(), d_hist, hist_n * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -738,12 +580,12 @@ int fcu_obf_prepass(fcu_ctx *c, int n_frames, const uint8_t *dev_y, int16_t *dev
   for (size_t k = 0; k < (size_t)n_frames * 15; k++)           /* the clamp bin is unreachable for 8-bit sources (|coef/8| <= 4080) */
     if (hist[k * OBF_HB + OBF_HB - 1]) { return fail(FCU_ERR_ARG, "fcu_obf_prepass: amplitude beyond the histogram (not an 8-bit plane?)"); }
   HIPCHK(hipMemcpyAsync(d_thr, thr.data(), thr.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(e[2], st));
+  HIPCHK(ev.record(2));
   hipLaunchKernelGGL(obf_count, grid, dim3(OBF_THREADS), 0, st, dev_y, w, h, frame_bytes, d_thr, dev_obf);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e[3], st));
+  HIPCHK(ev.record(3));
   HIPCHK(hipStreamSynchronize(st));
-  if (kernel_ms2) { hipEventElapsedTime(&kernel_ms2[0], e[0], e[1]); hipEventElapsedTime(&kernel_ms2[1], e[2], e[3]); }
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 2, 3); }
   if (host_yc) memcpy(host_yc, yc.data(), yc.size() * sizeof(double));
   return FCU_OK;
 }
@@ -754,7 +596,7 @@ int fcu_obf_prepass(fcu_ctx *c, int n_frames, const uint8_t *dev_y, int16_t *dev
 static int lf_tiles_arg(const fcu_ctx *c, int n_cols, int n_rows, int lf_cross_tiles, const char *name, LfTiles &T)
 {
   if (lf_cross_tiles != 0 && lf_cross_tiles != 1) return fail(FCU_ERR_ARG, std::string(name) + ": lf_cross_tiles (LFCrossTileBoundaryFlag) is 0 or 1");
-  const int W = (c->sp.width + 63) / 64, H = (c->sp.height + 63) / 64;
+  const int W = c->hs.w_ctu, H = c->hs.h_ctu;
   if (!tile_grid(W, H, n_cols, n_rows, nullptr, nullptr)) return fail(FCU_ERR_ARG, std::string(name) + ": a grid needs 1 <= n_cols <= width and 1 <= n_rows <= height in CTUs (no empty tile)");
   if (!lf_tiles_fill(T, W, H, n_cols, n_rows, lf_cross_tiles)) return fail(FCU_ERR_ARG, std::string(name) + ": pictures beyond 256 CTUs in width or height are not supported with tiles");
   return FCU_OK;
@@ -766,30 +608,27 @@ static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const fcu
 {
   if (!dev_out || !dev_rec_y || !dev_rec_u || !dev_rec_v) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
   if (beta_offset_div2 < -6 || beta_offset_div2 > 6 || tc_offset_div2 < -6 || tc_offset_div2 > 6) return fail(FCU_ERR_ARG, std::string(name) + ": offsets are limited to [-6, 6]");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64;
+  const int w = c->hs.sp.width, h = c->hs.sp.height, w_ctu = c->hs.w_ctu;
   const unsigned n0 = (unsigned)((w >> 3) * (h >> 2)), n1 = (unsigned)((w >> 2) * (h >> 3));
-  hipEvent_t e[3] = { nullptr, nullptr, nullptr };
-  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
-  if (kernel_ms2) { for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
   /* all vertical edges of the picture before the first horizontal one (TComLoopFilter.cpp:133-154): stream order */
   const dim3 g0((n0 + DBK_THREADS - 1) / DBK_THREADS), g1((n1 + DBK_THREADS - 1) / DBK_THREADS);
   if (T) hipLaunchKernelGGL((dbk_pass<0, true>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
   else hipLaunchKernelGGL((dbk_pass<0, false>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
   HIPCHK(hipGetLastError());
-  if (kernel_ms2) HIPCHK(hipEventRecord(e[1], st));
+  HIPCHK(ev.record(1));
   if (T) hipLaunchKernelGGL((dbk_pass<1, true>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
   else hipLaunchKernelGGL((dbk_pass<1, false>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
   HIPCHK(hipGetLastError());
-  if (kernel_ms2) {
-    HIPCHK(hipEventRecord(e[2], st));
-    HIPCHK(hipStreamSynchronize(st));
-    hipEventElapsedTime(&kernel_ms2[0], e[0], e[1]); hipEventElapsedTime(&kernel_ms2[1], e[1], e[2]);
-  }
+  HIPCHK(ev.record(2));
+  if (kernel_ms2) { HIPCHK(hipStreamSynchronize(st)); ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
   return FCU_OK;
 }
 
+static size_t up(size_t v) { return (v + 255) & ~(size_t)255; }      /* sub-blocks of a DevBuf start at multiples of 256 bytes */
 /* fcu_sao (T null: the kernels without a grid) and fcu_sao_tiles */
 static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
                    fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
@@ -803,21 +642,17 @@ static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, 
     if (T && params[i].slice_ctus != 0) return fail(FCU_ERR_ARG, name + ": tiles need one slice per picture (slice_ctus 0)");
     if (!(params[i].lambda[0] > 0) || params[i].lambda[1] < 0 || params[i].lambda[2] < 0) return fail(FCU_ERR_ARG, name + ": lambda[0] must be positive");
   }
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64, n_ctu = c->n_ctu;
+  const int w = c->hs.sp.width, h = c->hs.sp.height, w_ctu = c->hs.w_ctu, n_ctu = c->hs.n_ctu;
   if (w_ctu + 1 > SAO_RING) return fail(FCU_ERR_ARG, name + ": pictures wider than 255 CTUs are not supported (sao_decide's neighbour ring)");
   const size_t plane[3] = { (size_t)w * h, (size_t)(w / 2) * (h / 2), (size_t)(w / 2) * (h / 2) }, pic_bytes = plane[0] + 2 * plane[1];
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_pics = 0, o_src = up(o_pics + sizeof(SaoPic) * n_pics), o_stats = up(o_src + pic_bytes * n_pics),
                o_cand = up(o_stats + sizeof(int32_t) * SAO_STAT_INTS * 3 * (size_t)n_ctu * n_pics),
                o_recon = up(o_cand + sizeof(SaoCand) * 15 * (size_t)n_ctu * n_pics),
                o_off = up(o_recon + sizeof(fcu_sao_ctu) * (size_t)n_ctu * n_pics), total = up(o_off + sizeof(int32_t) * 3 * n_pics);
-  if (total > c->sao_cap) {
-    if (c->d_sao) { HIPCHK(hipStreamSynchronize(st)); hipFree(c->d_sao); c->d_sao = nullptr; c->sao_cap = 0; }
-    HIPCHK(hipMalloc(&c->d_sao, total)); c->sao_cap = total;
-  }
-  uint8_t *base = (uint8_t *)c->d_sao;
+  HIPCHK(c->sao.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->sao.p;
   SaoPic *d_pics = (SaoPic *)(base + o_pics); int32_t *d_stats = (int32_t *)(base + o_stats); SaoCand *d_cand = (SaoCand *)(base + o_cand);
   fcu_sao_ctu *d_recon = (fcu_sao_ctu *)(base + o_recon); int32_t *d_off = (int32_t *)(base + o_off);
   std::vector<SaoPic> hp((size_t)n_pics);
@@ -835,28 +670,27 @@ static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, 
     hp[i].slice_type = params[i].slice_type; hp[i].qp = params[i].qp; hp[i].slice_ctus = params[i].slice_ctus;
   }
   HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(SaoPic) * n_pics, hipMemcpyHostToDevice, st));
-  hipEvent_t e[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 5; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
-  if (kernel_ms4) { for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
+  Events ev(st, kernel_ms4 != nullptr);
+  HIPCHK(ev.create(5)); HIPCHK(ev.record(0));
   if (T) hipLaunchKernelGGL(sao_stats_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu, *T);
   else hipLaunchKernelGGL(sao_stats, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
-  if (kernel_ms4) HIPCHK(hipEventRecord(e[1], st));
+  HIPCHK(ev.record(1));
   const long long n_cand = (long long)n_pics * n_ctu * 15;
   hipLaunchKernelGGL(sao_cands, dim3((unsigned)((n_cand + SAO_THREADS - 1) / SAO_THREADS)), dim3(SAO_THREADS), 0, st, d_pics, d_stats, d_cand, n_ctu, n_pics);
   HIPCHK(hipGetLastError());
-  if (kernel_ms4) HIPCHK(hipEventRecord(e[2], st));
+  HIPCHK(ev.record(2));
   if (T) hipLaunchKernelGGL(sao_decide_tiles, dim3(n_pics), dim3(64), 0, st, d_pics, d_stats, d_cand, dev_coded, d_recon, d_off, w_ctu, n_ctu, n_pics, *T);
   else hipLaunchKernelGGL(sao_decide, dim3(n_pics), dim3(64), 0, st, d_pics, d_stats, d_cand, dev_coded, d_recon, d_off, w_ctu, n_ctu, n_pics);
   HIPCHK(hipGetLastError());
-  if (kernel_ms4) HIPCHK(hipEventRecord(e[3], st));
+  HIPCHK(ev.record(3));
   if (T) hipLaunchKernelGGL(sao_apply_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu, *T);
   else hipLaunchKernelGGL(sao_apply, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
-  if (kernel_ms4) HIPCHK(hipEventRecord(e[4], st));
+  HIPCHK(ev.record(4));
   if (off_count) HIPCHK(hipMemcpyAsync(off_count, d_off, sizeof(int32_t) * 3 * n_pics, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and off_count are done with */
-  if (kernel_ms4) for (int i = 0; i < 4; i++) hipEventElapsedTime(&kernel_ms4[i], e[i], e[i + 1]);
+  if (kernel_ms4) for (int i = 0; i < 4; i++) ev.ms(&kernel_ms4[i], i, i + 1);
   return FCU_OK;
 }
 
@@ -922,17 +756,13 @@ int fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, co
     if (!dev_rec[i]) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_rec[" + std::to_string(i) + "] is null");
   }
   for (int i = 0; i < n_pics; i++) if (!dev_out[i]) return fail(FCU_ERR_ARG, "fcu_picture_report: dev_out[" + std::to_string(i) + "] is null");
-  HIPCHK(hipSetDevice(c->sp.device));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
-  const int w = c->sp.width, h = c->sp.height, w_ctu = (w + 63) / 64, n_ctu = c->n_ctu;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const int w = c->hs.sp.width, h = c->hs.sp.height, w_ctu = c->hs.w_ctu, n_ctu = c->hs.n_ctu;
   const size_t o_pics = 0, o_rep = up(o_pics + sizeof(ReportPic) * n_pics), o_ctu = up(o_rep + sizeof(fcu_pic_report) * n_pics),
                total = dev_ctu ? o_ctu : up(o_ctu + sizeof(fcu_ctu_report) * (size_t)n_ctu * n_pics);
-  if (total > c->rep_cap) {
-    if (c->d_rep) { HIPCHK(hipStreamSynchronize(st)); hipFree(c->d_rep); c->d_rep = nullptr; c->rep_cap = 0; }
-    HIPCHK(hipMalloc(&c->d_rep, total)); c->rep_cap = total;
-  }
-  uint8_t *base = (uint8_t *)c->d_rep;
+  HIPCHK(c->rep.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->rep.p;
   ReportPic *d_pics = (ReportPic *)(base + o_pics); fcu_pic_report *d_rep = (fcu_pic_report *)(base + o_rep);
   fcu_ctu_report *d_ctu = dev_ctu ? dev_ctu : (fcu_ctu_report *)(base + o_ctu);
   std::vector<ReportPic> hp((size_t)n_pics);
@@ -942,19 +772,18 @@ int fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, co
   }
   const bool wide = report_wide_ok(w, hp.data(), n_pics);
   HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(ReportPic) * n_pics, hipMemcpyHostToDevice, st));
-  hipEvent_t e[3] = { nullptr, nullptr, nullptr };
-  struct EventGuard { hipEvent_t *e; ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) hipEventDestroy(e[i]); } } guard{ e };
-  if (kernel_ms2) { for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&e[i])); HIPCHK(hipEventRecord(e[0], st)); }
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
   if (wide) hipLaunchKernelGGL(report_ctu<true>, dim3(n_ctu, n_pics), dim3(REP_THREADS), 0, st, d_pics, d_ctu, w, h, w_ctu, n_ctu);
   else hipLaunchKernelGGL(report_ctu<false>, dim3(n_ctu, n_pics), dim3(REP_THREADS), 0, st, d_pics, d_ctu, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
-  if (kernel_ms2) HIPCHK(hipEventRecord(e[1], st));
+  HIPCHK(ev.record(1));
   hipLaunchKernelGGL(report_pic, dim3(n_pics), dim3(REP_THREADS), 0, st, d_ctu, d_rep, w, h, n_ctu);
   HIPCHK(hipGetLastError());
-  if (kernel_ms2) HIPCHK(hipEventRecord(e[2], st));
+  HIPCHK(ev.record(2));
   HIPCHK(hipMemcpyAsync(host_reports, d_rep, sizeof(fcu_pic_report) * n_pics, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and host_reports are done with */
-  if (kernel_ms2) { hipEventElapsedTime(&kernel_ms2[0], e[0], e[1]); hipEventElapsedTime(&kernel_ms2[1], e[1], e[2]); }
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
   for (int i = 0; i < n_pics; i++) for (int k = 0; k < 3; k++) host_reports[i].psnr[k] = report_psnr(host_reports[i].ssd[k], host_reports[i].n_samples[k]);
   return FCU_OK;
 }

@@ -226,7 +226,7 @@ int  fcu_wpp_begin_slices(fcu_ctx *c, int first_chain, const fcu_frame_params *f
                           const uint8_t *dev_org_y, const uint8_t *dev_org_u, const uint8_t *dev_org_v,
                           uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v, fcu_ctu_out *dev_out);
 /* Decide every row chain in [first, first + n) to the end, in one launch on `hip_stream`.  The range must hold whole pictures
- * bound by fcu_wpp_begin(_p) or fcu_wpp_begin_slices and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin; also for a P
+ * bound by fcu_wpp_begin(_p), fcu_wpp_begin_slices or fcu_wpp_begin_tiles and not yet decided (else FCU_ERR_STATE, as for a chain not bound by fcu_wpp_begin; also for a P
  * row without a reference picture, or whose references or collocated field differ from its row 0's).  It may hold more
  * chains than the GPU keeps resident.  Returns when the launch has finished; FCU_ERR_STATE if a row gave up waiting for the
  * row above (a bounded wait of 120 s; the pictures of the launch are then undefined). */
