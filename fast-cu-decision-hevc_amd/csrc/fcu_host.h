@@ -239,6 +239,82 @@ inline double report_psnr(uint64_t ssd, uint64_t n)
   return ssd ? 10.0 * log10(ref / (double)ssd) : 999.99;
 }
 
+/* ---- The picture hash (fcu_hash.h, fcu_picture_hash): the arithmetic of HM's picture CRC (compCRC, TComPicYuvMD5.cpp:89-127) in
+ * GF(2)[x] mod P, P = x^16 + x^12 + x^5 + 1.  compCRC shifts the message bits in at the low end, so a state is a polynomial of
+ * degree < 16 and one message bit b takes s to s x + b: a message M of n bits takes s to s x^n + M(x), and the digest is that
+ * state times x^16 (the sixteen flushed zero bits).  Hence for a message AB: state(AB, s) = state(A, s) x^|B| + state(B, 0) -- the
+ * fold the kernels use; the initial state contributes 0xffff x^n, which is host arithmetic (crc_adv).  All constexpr: the kernels
+ * take their multipliers x^n as compile-time constants, and the byte table is computed from the polynomial. */
+enum { CRC_POLY = 0x1021, CRC_INIT = 0xffff };
+/* a b mod P */
+constexpr uint32_t crc_mul(uint32_t a, uint32_t b)
+{
+  uint32_t r = 0;
+  for (int i = 0; i < 16; i++) {
+    if ((b >> i) & 1u) r ^= a;
+    a = ((a << 1) & 0xffffu) ^ ((a & 0x8000u) ? (uint32_t)CRC_POLY : 0u);
+  }
+  return r;
+}
+/* x^n mod P */
+constexpr uint32_t crc_xpow(uint64_t n)
+{
+  uint32_t r = 1, sq = 2;
+  for (; n; n >>= 1) { if (n & 1u) r = crc_mul(r, sq); sq = crc_mul(sq, sq); }
+  return r;
+}
+/* state s after n_bits zero bits */
+constexpr uint32_t crc_adv(uint32_t s, uint64_t n_bits) { return crc_mul(s, crc_xpow(n_bits)); }
+/* entry h of the byte table: h x^16 mod P, the part of a state that leaves the register when a byte is shifted in */
+constexpr uint16_t crc_tab_entry(uint32_t h) { return (uint16_t)crc_mul(h, crc_xpow(16)); }
+struct CrcTab { uint16_t t[256]; };
+constexpr CrcTab crc_make_tab() { CrcTab T = {}; for (uint32_t h = 0; h < 256; h++) T.t[h] = crc_tab_entry(h); return T; }
+/* state s after the byte v: s x^8 + v */
+constexpr uint32_t crc_byte(const CrcTab &T, uint32_t s, uint32_t v) { return ((s << 8) & 0xffffu) ^ v ^ T.t[s >> 8]; }
+/* the serial definition on the host: the state after n bytes, and the digest of a whole message */
+inline uint32_t crc_bytes(uint32_t s, const uint8_t *p, size_t n)
+{
+  static constexpr CrcTab T = crc_make_tab();
+  for (size_t i = 0; i < n; i++) s = crc_byte(T, s, p[i]);
+  return s;
+}
+inline uint32_t crc_digest(const uint8_t *p, size_t n) { return crc_adv(crc_bytes(CRC_INIT, p, n), 16); }
+
+/* fcu_hash_string: digestToString (TComPicYuvMD5.cpp:209-225) of one kind of a record -- the three planes' digests in hex, joined
+ * by ','.  Returns the length, FCU_ERR_ARG for a kind that is not exactly one of the three bits or a buffer too short for the
+ * string and its terminator. */
+inline int hash_string(const fcu_pic_hash *h, int kind, char *buf, int buf_len)
+{
+  if (!h || !buf) return FCU_ERR_ARG;
+  const uint8_t *d; int n;
+  if (kind == FCU_HASH_MD5) { d = &h->md5[0][0]; n = 16; }
+  else if (kind == FCU_HASH_CRC) { d = &h->crc[0][0]; n = 2; }
+  else if (kind == FCU_HASH_CHECKSUM) { d = &h->checksum[0][0]; n = 4; }
+  else return FCU_ERR_ARG;
+  const int len = 3 * 2 * n + 2;
+  if (buf_len < len + 1) return FCU_ERR_ARG;
+  static const char hex[] = "0123456789abcdef";
+  char *o = buf;
+  for (int pos = 0; pos < 3 * n; pos++) {
+    if (pos % n == 0 && pos != 0) *o++ = ',';
+    *o++ = hex[d[pos] >> 4]; *o++ = hex[d[pos] & 15];
+  }
+  *o = 0;
+  return len;
+}
+/* fcu_picture_hash: what it refuses, with the argument named; FCU_OK otherwise */
+inline int hash_args_check(int n_pics, int kinds, const uint8_t *const *dev_planes, const fcu_pic_hash *host_hashes, std::string &err)
+{
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (kinds == 0 || (kinds & ~(FCU_HASH_MD5 | FCU_HASH_CRC | FCU_HASH_CHECKSUM))) bad = "kinds is a non-empty mask of FCU_HASH_MD5 | FCU_HASH_CRC | FCU_HASH_CHECKSUM";
+  else if (!dev_planes) bad = "dev_planes is null";
+  else if (!host_hashes) bad = "host_hashes is null";
+  if (bad) { err = std::string("fcu_picture_hash: ") + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < 3 * n_pics; i++) if (!dev_planes[i]) { err = "fcu_picture_hash: dev_planes[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+
 /* ---- The byte ranges { offset, length } of the descriptor libfcu.so copies to the device on their own, named once: a setter
  * uploads the range it has written and nothing else, so a chain's position, coder state and counters on the device stay. */
 struct ChainRange { size_t off, len; };

@@ -20,6 +20,7 @@
 #include "fcu_deblock.h"
 #include "fcu_sao.h"
 #include "fcu_report.h"
+#include "fcu_hash.h"
 
 using namespace fcu;
 
@@ -116,6 +117,7 @@ struct fcu_ctx {
   DevBuf hist, thr;                /* fcu_obf_prepass: histograms, thresholds */
   DevBuf sao;                      /* fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
   DevBuf rep;                      /* fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
+  DevBuf hash;                     /* fcu_picture_hash: plane pointers, hash records, per-chunk partials */
   /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
    * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
   DevBuf wpp_ctl, wpp_sync;
@@ -193,6 +195,7 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_PU_TRACE: return (int)sizeof(fcu_pu_trace);
   case FCU_ABI_PIC_REPORT: return (int)sizeof(fcu_pic_report);
   case FCU_ABI_CTU_REPORT: return (int)sizeof(fcu_ctu_report);
+  case FCU_ABI_PIC_HASH: return (int)sizeof(fcu_pic_hash);
   default: return -1;
   }
 }
@@ -227,7 +230,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p);
   hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
@@ -786,6 +789,57 @@ int fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, co
   if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
   for (int i = 0; i < n_pics; i++) for (int k = 0; k < 3; k++) host_reports[i].psnr[k] = report_psnr(host_reports[i].ssd[k], host_reports[i].n_samples[k]);
   return FCU_OK;
+}
+
+/* calcMD5 / calcCRC / calcChecksum of n_pics pictures: hash_chunk + hash_fold and / or hash_md5 (fcu_hash.h), the records back */
+int fcu_picture_hash(fcu_ctx *c, int n_pics, int kinds, const uint8_t *const *dev_planes, fcu_pic_hash *host_hashes, float *kernel_ms3, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_picture_hash: null context");
+  { std::string err; const int rc = hash_args_check(n_pics, kinds, dev_planes, host_hashes, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const uint32_t w[3] = { (uint32_t)c->hs.sp.width, (uint32_t)c->hs.sp.width / 2, (uint32_t)c->hs.sp.width / 2 },
+                 h[3] = { (uint32_t)c->hs.sp.height, (uint32_t)c->hs.sp.height / 2, (uint32_t)c->hs.sp.height / 2 };
+  const HashGeom G = hash_geom(3, w, h, kinds);
+  const size_t o_planes = 0, o_hash = up(o_planes + sizeof(void *) * 3 * n_pics), o_part = up(o_hash + sizeof(fcu_pic_hash) * n_pics),
+               total = up(o_part + sizeof(HashPartial) * (size_t)G.per_pic * n_pics);
+  HIPCHK(c->hash.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->hash.p;
+  const uint8_t **d_planes = (const uint8_t **)(base + o_planes); fcu_pic_hash *d_hash = (fcu_pic_hash *)(base + o_hash); HashPartial *d_part = (HashPartial *)(base + o_part);
+  const bool wide = hash_wide_ok(dev_planes, 3 * n_pics), sums = (kinds & (FCU_HASH_CRC | FCU_HASH_CHECKSUM)) != 0, md5 = (kinds & FCU_HASH_MD5) != 0;
+  HIPCHK(hipMemcpyAsync(d_planes, dev_planes, sizeof(void *) * 3 * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms3 != nullptr);
+  HIPCHK(ev.create(4)); HIPCHK(ev.record(0));
+  if (sums) {
+    if (wide) hipLaunchKernelGGL(hash_chunk<16>, dim3(G.per_pic, n_pics), dim3(HASH_THREADS), 0, st, d_planes, d_part, G);
+    else hipLaunchKernelGGL(hash_chunk<1>, dim3(G.per_pic, n_pics), dim3(HASH_THREADS), 0, st, d_planes, d_part, G);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(ev.record(1));
+  if (sums) { hipLaunchKernelGGL(hash_fold, dim3(3, n_pics), dim3(HASH_THREADS), 0, st, d_part, d_hash, G); HIPCHK(hipGetLastError()); }
+  HIPCHK(ev.record(2));
+  if (md5) {
+    const int n_streams = 3 * n_pics; const dim3 grid((unsigned)((n_streams + HASH_MD5_THREADS - 1) / HASH_MD5_THREADS));
+    if (wide) hipLaunchKernelGGL(hash_md5<16>, grid, dim3(HASH_MD5_THREADS), 0, st, d_planes, d_hash, G, n_streams);
+    else hipLaunchKernelGGL(hash_md5<1>, grid, dim3(HASH_MD5_THREADS), 0, st, d_planes, d_hash, G, n_streams);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(ev.record(3));
+  HIPCHK(hipMemcpyAsync(host_hashes, d_hash, sizeof(fcu_pic_hash) * n_pics, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* dev_planes (the caller's array) and host_hashes are done with */
+  for (int i = 0; i < n_pics; i++) hash_clear_unasked(host_hashes[i], kinds);
+  if (kernel_ms3) {
+    kernel_ms3[0] = kernel_ms3[1] = kernel_ms3[2] = 0.f;
+    if (sums) { ev.ms(&kernel_ms3[0], 0, 1); ev.ms(&kernel_ms3[1], 1, 2); }
+    if (md5) ev.ms(&kernel_ms3[2], 2, 3);
+  }
+  return FCU_OK;
+}
+
+int fcu_hash_string(const fcu_pic_hash *h, int kind, char *buf, int buf_len)
+{
+  const int rc = hash_string(h, kind, buf, buf_len);
+  return rc < 0 ? fail(rc, "fcu_hash_string: kind is exactly one of FCU_HASH_MD5 / FCU_HASH_CRC / FCU_HASH_CHECKSUM and the buffer holds the string (MD5: 99 bytes)") : rc;
 }
 
 } /* extern "C" */

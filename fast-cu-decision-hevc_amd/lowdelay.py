@@ -58,7 +58,7 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
@@ -68,8 +68,13 @@ class LowDelayPDecider:
         tile boundaries and SAO reads samples across them (fcu_deblock_tiles / fcu_sao_tiles).  None means 1 for deblocking,
         HM's default; sao=True together with tiles asks for an explicit choice.
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
-        statistics) of the final planes, taken on the device in one batched call for all clips."""
+        statistics) of the final planes, taken on the device in one batched call for all clips.
+        pic_hash="md5", "crc" or "checksum": every result dict gains `hash`, HM's decoded-picture hash string of the final planes
+        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call for all clips."""
         self.do_report = report
+        if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
+            raise ValueError("LowDelayPDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
+        self.pic_hash = pic_hash
         self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, tmvp=tmvp, who="LowDelayPDecider")
         self.tiles, self.lf_cross_tiles, self.wpp, self.slice_rows, self.slice_ctus = tiles, lo.lf_cross_tiles, wpp, slice_rows, lo.slice_ctus
         self.n_slices, self.n_chains, self.sao_slice_ctus = lo.n_slices, lo.chains, lo.sao_slice_ctus
@@ -138,6 +143,9 @@ class LowDelayPDecider:
         if self.do_report:                                   # on the final planes: after the loop filters that are enabled
             for r, rep in zip(res, eng.report([{"org": eng.org_planes(r["first"]), "rec": r["rec"], "out": r["out"]} for r in res])):
                 r["report"] = rep
+        if self.pic_hash:                                    # on the final planes as well, nothing but the digests comes back
+            for r, d in zip(res, eng.picture_hash(res, kinds=(self.pic_hash,))):
+                r["hash"] = d["line"][self.pic_hash]
         for s, r in enumerate(res):
             self.col[s] = r["out"]                           # stays in HBM: the next picture's collocated motion field
             self.ref[s] = eng.pad_reference(r["rec"])          # reference of the next picture of this clip

@@ -79,7 +79,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -95,8 +95,13 @@ class SequenceDecider:
         crosses the tile boundaries.  PictureLayout holds the rules of these combinations.  This driver runs no SAO: sao=True
         together with tiles is refused whatever lf_cross_tiles says.
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
-        statistics) of the final planes, taken on the device in one batched call for the pictures of a group."""
+        statistics) of the final planes, taken on the device in one batched call for the pictures of a group.
+        pic_hash="md5", "crc" or "checksum": every result dict gains `hash`, HM's decoded-picture hash string of the final planes
+        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call per group."""
         self.do_report = report
+        if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
+            raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
+        self.pic_hash = pic_hash
         sao = flags.get("sao")
         self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, who="SequenceDecider")
         if sao and tiles is not None:
@@ -150,6 +155,9 @@ class SequenceDecider:
         if self.do_report:                                   # on the final planes: after the deblocking when it is enabled
             for p, rep in zip(pics, eng.report([{"org": eng.org_planes(p["first"]), "rec": p["rec"], "out": p["out"]} for p in pics])):
                 p["report"] = rep
+        if self.pic_hash:                                    # on the final planes as well, nothing but the digests comes back
+            for p, d in zip(pics, eng.picture_hash(pics, kinds=(self.pic_hash,))):
+                p["hash"] = d["line"][self.pic_hash]
         eng.sync()
         for p in pics:
             p["depth"] = p["out"].view(eng.n_ctu, nb)[:, :256].cpu().numpy().copy()      # fcu_ctu_out.depth leads the struct

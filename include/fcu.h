@@ -40,6 +40,9 @@
  *      TComDataCU.cpp:422-440,1071-1390)
  *   TEncGOP::xCalculateAddPSNR                     fcu_picture_report (SSD per plane -> PSNR, bits, bins, distortion and CU
  *     (TEncGOP.cpp:2195-2290)                        statistics of decided, filtered pictures; per CTU and per picture)
+ *   calcMD5 / calcCRC / calcChecksum,               fcu_picture_hash (the decoded-picture hash of reconstructed pictures, per
+ *     digestToString (TComPicYuvMD5.cpp:44-225,       plane, as the encoder prints it at the end of the picture line),
+ *      TEncGOP.cpp:1619-1640,1742-1756)               fcu_hash_string (the printed form)
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -408,6 +411,34 @@ int  fcu_picture_report(fcu_ctx *c, int n_pics, const uint8_t *const *dev_org, c
                         const fcu_ctu_out *const *dev_out, fcu_pic_report *host_reports, fcu_ctu_report *dev_ctu,
                         float *kernel_ms2, void *hip_stream);
 
+/* ---- the picture hash: the decoded-picture hash of HM (SEIDecodedPictureHash 1 / 2 / 3; calcMD5, calcCRC, calcChecksum of
+ * TComPicYuvMD5.cpp:44-207) of reconstructed pictures, taken where they are, in HBM -- what the encoder prints as ` [MD5:...]`,
+ * ` [CRC:...]` or ` [Checksum:...]` at the end of a picture line (TEncGOP.cpp:1742-1756).  Every plane is hashed on its own, in
+ * the order Y, Cb, Cr:
+ *   MD5       RFC 1321 over the plane's width x height bytes in raster order
+ *   CRC       16 bits, polynomial 0x1021, initial state 0xffff, the bits of every sample shifted in at the low end MSB first,
+ *             sixteen zero bits flushed at the end
+ *   checksum  the sum mod 2^32 over the samples of sample ^ (uint8)((x & 255) ^ (y & 255) ^ (x >> 8) ^ (y >> 8))
+ * The record holds the bytes in HM's digest order (crc and checksum high byte first): the hex of the bytes is HM's string. */
+enum { FCU_HASH_MD5 = 1, FCU_HASH_CRC = 2, FCU_HASH_CHECKSUM = 4 };   /* bit mask; HM's SEIDecodedPictureHash 1 / 2 / 3 */
+typedef struct fcu_pic_hash { uint8_t md5[3][16], crc[3][2], checksum[3][4], pad[2]; } fcu_pic_hash;      /* 68 B, no implicit padding */
+/* Hashes of n_pics pictures of this context's size.  dev_planes: host array of 3 * n_pics device pointers (Y, U, V of picture
+ * 0, then picture 1 ...); planes are dense (stride = width) and may start at any byte (16-byte aligned planes take 16-byte
+ * loads).  kinds: the mask of the hashes wanted; only those are computed, the fields of the others are zero.  host_hashes
+ * receives n_pics records.  Nothing is modified but the outputs; no atomics and no buffer that must be cleared: the same input
+ * gives the same bytes.  CRC and checksum share one pass over the samples (one kernel that leaves a partial result per 16 KiB of
+ * a plane, one that folds them); MD5 is a third kernel (one lane per plane: a serial chain of 64-byte blocks), launched only
+ * when asked for.  The call returns after they have finished and the records are on the host; kernel_ms3 (may be NULL)
+ * receives the durations of the three kernels, 0 for one that was not launched.
+ * FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1, kinds 0 or with other bits, a NULL dev_planes, a NULL
+ * entry of it, a NULL host_hashes.  No CPU fallback. */
+int  fcu_picture_hash(fcu_ctx *c, int n_pics, int kinds, const uint8_t *const *dev_planes, fcu_pic_hash *host_hashes,
+                      float *kernel_ms3, void *hip_stream);
+/* digestToString (TComPicYuvMD5.cpp:209-225) of one kind of a record: the three planes' digests in hex, joined by ','.  Pure
+ * host.  Returns the length of the string; FCU_ERR_ARG for a kind that is not exactly one of the three bits or a buffer too
+ * short for the string and its terminator (MD5 needs 99 bytes). */
+int  fcu_hash_string(const fcu_pic_hash *h, int kind, char *buf, int buf_len);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -442,7 +473,8 @@ const char *fcu_build_info(void);
 /* sizeof() of the ABI's structures as this library was compiled, by FCU_ABI_* index (-1 for an unknown index): a binding
  * in another language (ctypes, cgo, JNI) checks its own layouts against them before the first call; tests/test_cabi.py does. */
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
-       FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9 };
+       FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9,
+       FCU_ABI_PIC_HASH = 10 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus

@@ -19,6 +19,9 @@ every tile are decided concurrently as well; --lf-cross-tiles 0 makes the debloc
 LFCrossTileBoundaryFlag, default 1).  The slice mode is echoed on every picture line.
 --report takes the picture line's figures from the device (fcu_picture_report): the PSNR, the picture's bits and the shares of
 intra / skipped / merged area; the reconstruction is then copied to the host only when --rec asks for the file.
+--hash md5|crc|checksum appends the decoded-picture hash of the reconstruction to the picture line exactly as the reference encoder
+prints it with SEIDecodedPictureHash 1 / 2 / 3 (` [MD5:...]`, ` [CRC:...]`, ` [Checksum:...]`, TEncGOP.cpp:1746-1754), taken on the
+device (fcu_picture_hash): with --report --hash and no --rec no plane is copied to the host.
 """
 import argparse
 import os
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--tiles", default=None, metavar="CxR", help="one slice per picture cut into C x R uniform tiles decided as chains; with --wpp, WaveFrontSynchro inside every tile")
     ap.add_argument("--lf-cross-tiles", type=int, choices=(0, 1), default=None, help="with --tiles: LFCrossTileBoundaryFlag of the deblocking (default 1: the tile boundaries are filtered)")
     ap.add_argument("--report", action="store_true", help="PSNR, bits and intra / skip / merge shares per picture from the device report; no plane is copied to the host unless --rec is given")
+    ap.add_argument("--hash", choices=("md5", "crc", "checksum"), default=None, help="append HM's decoded-picture hash of the reconstruction to the picture line, taken on the device")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     args = ap.parse_args()
@@ -67,7 +71,7 @@ def main():
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
-        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report,
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report, pic_hash=args.hash,
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
@@ -94,18 +98,19 @@ def main():
             if args.report:                                    # the sums were formed on the device: nothing but the report came back
                 rep = r["report"]
                 psnr = [float(v) for v in rep["psnr"]]
-                n = max(int(rep["n_part"]), 1)
-                more = (f"  bits {int(rep['bits'])}  intra {100.0 * int(rep['intra_part']) / n:.1f}% skip {100.0 * int(rep['skip_part']) / n:.1f}% "
-                        f"merge {100.0 * int(rep['merge_part']) / n:.1f}%")
+                parts = max(int(rep["n_part"]), 1)
+                more = (f"  bits {int(rep['bits'])}  intra {100.0 * int(rep['intra_part']) / parts:.1f}% skip {100.0 * int(rep['skip_part']) / parts:.1f}% "
+                        f"merge {100.0 * int(rep['merge_part']) / parts:.1f}%")
             else:
                 for p, o in zip(r["rec"], yuv):
                     d = p.cpu().numpy().astype(np.int64) - o.astype(np.int64)
                     ssd = float((d * d).sum())
                     psnr.append(999.99 if ssd == 0 else 10.0 * np.log10(255.0 * 255.0 * d.size / ssd))
+            digest = pkg.engine.hash_line(args.hash, r["hash"]) if args.hash else ""
             hist = np.bincount(r["depth"].ravel(), minlength=4)
             print(f"POC {r['poc']:4d} {names[r['state']]:9s} [{dec.slice_mode}] skip2Nx2N={r['sw_skip'].tolist()} terminate={r['sw_term'].tolist()} "
                   f"partitions at depth 0..3 = {hist.tolist()}  TU trials {r['tu_trials']}  "
-                  f"PSNR Y {psnr[0]:.4f} U {psnr[1]:.4f} V {psnr[2]:.4f} dB{more}", flush=True)
+                  f"PSNR Y {psnr[0]:.4f} U {psnr[1]:.4f} V {psnr[2]:.4f} dB{more}{digest}", flush=True)
             if rec_f:
                 seq.write_yuv420(rec_f, [p.cpu().numpy() for p in r["rec"]])
             if args.depth:
