@@ -315,6 +315,98 @@ inline int hash_args_check(int n_pics, int kinds, const uint8_t *const *dev_plan
   return FCU_OK;
 }
 
+/* ---- Decision maps and split match (fcu_maps.h, fcu_decision_maps, fcu_split_match): geometry and argument rules.
+ * maps_field_offset: byte offset of the 256-byte array of FCU_MAP_* id inside fcu_ctu_out, -1 for an unknown id */
+inline int maps_field_offset(int id)
+{
+  switch (id) {
+  case FCU_MAP_DEPTH: return (int)offsetof(fcu_ctu_out, depth);
+  case FCU_MAP_PART_SIZE: return (int)offsetof(fcu_ctu_out, part_size);
+  case FCU_MAP_PRED_MODE: return (int)offsetof(fcu_ctu_out, pred_mode);
+  case FCU_MAP_SKIP: return (int)offsetof(fcu_ctu_out, skip);
+  case FCU_MAP_MERGE_FLAG: return (int)offsetof(fcu_ctu_out, merge_flag);
+  case FCU_MAP_MERGE_IDX: return (int)offsetof(fcu_ctu_out, merge_idx);
+  case FCU_MAP_TR_IDX: return (int)offsetof(fcu_ctu_out, tr_idx);
+  case FCU_MAP_CBF_Y: case FCU_MAP_CBF_CB: case FCU_MAP_CBF_CR: return (int)offsetof(fcu_ctu_out, cbf) + FCU_NPART * (id - FCU_MAP_CBF_Y);
+  case FCU_MAP_TSKIP_Y: case FCU_MAP_TSKIP_CB: case FCU_MAP_TSKIP_CR: return (int)offsetof(fcu_ctu_out, tskip) + FCU_NPART * (id - FCU_MAP_TSKIP_Y);
+  case FCU_MAP_INTRA_DIR_LUMA: case FCU_MAP_INTRA_DIR_CHROMA: return (int)offsetof(fcu_ctu_out, intra_dir) + FCU_NPART * (id - FCU_MAP_INTRA_DIR_LUMA);
+  case FCU_MAP_QP: return (int)offsetof(fcu_ctu_out, qp);
+  case FCU_MAP_INTER_DIR: return (int)offsetof(fcu_ctu_out, inter_dir);
+  case FCU_MAP_MVP_IDX: return (int)offsetof(fcu_ctu_out, mvp_idx);
+  case FCU_MAP_REF_IDX: return (int)offsetof(fcu_ctu_out, ref_idx);
+  default: return -1;
+  }
+}
+/* what the kernels need to know of a batch: the picture, the arrays to read, and where level d of a picture's label / N_OBF
+ * maps starts (lvl_off[4] = their elements per picture) */
+struct MapsGeom {
+  int width, height, w_ctu, n_ctu, n_fields;
+  int lvl_w[4], lvl_off[5];
+  uint16_t field_off[FCU_MAP_FIELDS];
+};
+inline MapsGeom maps_geom(int width, int height, int n_fields, const int *field_ids)
+{
+  MapsGeom G = {};
+  G.width = width; G.height = height; G.w_ctu = (width + 63) / 64; G.n_ctu = G.w_ctu * ((height + 63) / 64); G.n_fields = n_fields;
+  for (int d = 0; d < 4; d++) {
+    const int s = 64 >> d;
+    G.lvl_w[d] = (width + s - 1) / s;
+    G.lvl_off[d + 1] = G.lvl_off[d] + G.lvl_w[d] * ((height + s - 1) / s);
+  }
+  for (int k = 0; k < n_fields; k++) G.field_off[k] = (uint16_t)maps_field_offset(field_ids[k]);
+  return G;
+}
+/* the unit the rows of the byte maps (and of the motion map) go out in: 16 bytes when every row of every map starts on 16 bytes
+ * -- W4 a multiple of 16 (whole CTU columns, every map a multiple of 16 bytes) and aligned bases --, else 2-byte units, which
+ * W4 even always allows; their alignment is the base's: 2, or 1 for a byte map at an odd address */
+inline int maps_row_align(int width, const void *dev_bytes, const void *dev_mv)
+{
+  const uintptr_t a = (uintptr_t)dev_bytes | (uintptr_t)dev_mv;
+  if ((width & 63) == 0 && (a & 15) == 0) return 16;
+  return (a & 1) ? 1 : 2;
+}
+/* fcu_decision_maps: what it refuses, with the argument named; FCU_OK otherwise */
+inline int maps_args_check(int n_pics, const fcu_ctu_out *const *dev_out, int n_fields, const int *field_ids, const void *dev_bytes, const void *dev_mv,
+                           const void *dev_labels, const int16_t *const *dev_obf, const void *dev_nobf, std::string &err)
+{
+  const std::string who = "fcu_decision_maps: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_out) bad = "dev_out is null";
+  else if (n_fields < 0 || n_fields > FCU_MAP_FIELDS) bad = "n_fields is 0 .. FCU_MAP_FIELDS";
+  else if (n_fields > 0 && !field_ids) bad = "field_ids is null";
+  else if (n_fields > 0 && !dev_bytes) bad = "dev_bytes is null although n_fields > 0";
+  else if (n_fields == 0 && dev_bytes) bad = "dev_bytes is given although n_fields is 0";
+  else if (dev_nobf && !dev_obf) bad = "dev_obf is null although dev_nobf is given";
+  else if (dev_obf && !dev_nobf) bad = "dev_nobf is null although dev_obf is given";
+  else if (((uintptr_t)dev_mv | (uintptr_t)dev_nobf) & 1) bad = "dev_mv and dev_nobf start at even bytes";
+  else if (n_fields == 0 && !dev_mv && !dev_labels && !dev_nobf) bad = "no output is wanted (n_fields 0, dev_mv, dev_labels and dev_nobf null)";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < n_pics; i++) if (!dev_out[i]) { err = who + "dev_out[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  for (int i = 0; dev_obf && i < n_pics; i++) if (!dev_obf[i]) { err = who + "dev_obf[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  for (int k = 0; k < n_fields; k++) {
+    if (maps_field_offset(field_ids[k]) < 0) { err = who + "field_ids[" + std::to_string(k) + "] = " + std::to_string(field_ids[k]) + " is no FCU_MAP_* id"; return FCU_ERR_ARG; }
+    for (int j = 0; j < k; j++) if (field_ids[j] == field_ids[k]) { err = who + "field_ids[" + std::to_string(k) + "] repeats field_ids[" + std::to_string(j) + "]"; return FCU_ERR_ARG; }
+  }
+  return FCU_OK;
+}
+/* fcu_split_match: likewise */
+inline int match_args_check(int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b, const fcu_pic_match *host_matches, std::string &err)
+{
+  const std::string who = "fcu_split_match: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_out_a) bad = "dev_out_a is null";
+  else if (!dev_out_b) bad = "dev_out_b is null";
+  else if (!host_matches) bad = "host_matches is null";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < n_pics; i++) {
+    if (!dev_out_a[i]) { err = who + "dev_out_a[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+    if (!dev_out_b[i]) { err = who + "dev_out_b[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  }
+  return FCU_OK;
+}
+
 /* ---- The byte ranges { offset, length } of the descriptor libfcu.so copies to the device on their own, named once: a setter
  * uploads the range it has written and nothing else, so a chain's position, coder state and counters on the device stay. */
 struct ChainRange { size_t off, len; };

@@ -21,6 +21,7 @@
 #include "fcu_sao.h"
 #include "fcu_report.h"
 #include "fcu_hash.h"
+#include "fcu_maps.h"
 
 using namespace fcu;
 
@@ -118,6 +119,7 @@ struct fcu_ctx {
   DevBuf sao;                      /* fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
   DevBuf rep;                      /* fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   DevBuf hash;                     /* fcu_picture_hash: plane pointers, hash records, per-chunk partials */
+  DevBuf maps;                     /* fcu_decision_maps / fcu_split_match: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
    * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
   DevBuf wpp_ctl, wpp_sync;
@@ -196,6 +198,8 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_PIC_REPORT: return (int)sizeof(fcu_pic_report);
   case FCU_ABI_CTU_REPORT: return (int)sizeof(fcu_ctu_report);
   case FCU_ABI_PIC_HASH: return (int)sizeof(fcu_pic_hash);
+  case FCU_ABI_CTU_MATCH: return (int)sizeof(fcu_ctu_match);
+  case FCU_ABI_PIC_MATCH: return (int)sizeof(fcu_pic_match);
   default: return -1;
   }
 }
@@ -230,7 +234,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p);
   hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
@@ -840,6 +844,67 @@ int fcu_hash_string(const fcu_pic_hash *h, int kind, char *buf, int buf_len)
 {
   const int rc = hash_string(h, kind, buf, buf_len);
   return rc < 0 ? fail(rc, "fcu_hash_string: kind is exactly one of FCU_HASH_MD5 / FCU_HASH_CRC / FCU_HASH_CHECKSUM and the buffer holds the string (MD5: 99 bytes)") : rc;
+}
+
+/* the decision as rasters: maps_ctu (fcu_maps.h), one launch for the batch */
+int fcu_decision_maps(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out, int n_fields, const int *field_ids, uint8_t *dev_bytes, int16_t *dev_mv,
+                      int8_t *dev_labels, const int16_t *const *dev_obf, uint16_t *dev_nobf, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_decision_maps: null context");
+  { std::string err; const int rc = maps_args_check(n_pics, dev_out, n_fields, field_ids, dev_bytes, dev_mv, dev_labels, dev_obf, dev_nobf, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, n_fields, field_ids);
+  HIPCHK(c->maps.reserve(up(sizeof(MapsPic) * n_pics), st));
+  MapsPic *d_pics = (MapsPic *)c->maps.p;
+  std::vector<MapsPic> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) { hp[i].out = dev_out[i]; hp[i].obf = dev_obf ? dev_obf[i] : nullptr; }
+  HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(MapsPic) * n_pics, hipMemcpyHostToDevice, st));
+  const MapsOut Q = { dev_bytes, dev_mv, dev_labels, dev_nobf };
+  const int align = maps_row_align(G.width, dev_bytes, dev_mv);
+  const dim3 grid(G.n_ctu, n_pics), block(MAPS_THREADS);
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  if (align == 16) hipLaunchKernelGGL((maps_ctu<16, 16>), grid, block, 0, st, d_pics, Q, G);
+  else if (align == 2) hipLaunchKernelGGL((maps_ctu<2, 2>), grid, block, 0, st, d_pics, Q, G);
+  else hipLaunchKernelGGL((maps_ctu<2, 1>), grid, block, 0, st, d_pics, Q, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) is done with */
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+/* the agreement of two decisions: match_ctu + match_pic (fcu_maps.h), the records back */
+int fcu_split_match(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b, fcu_pic_match *host_matches,
+                    fcu_ctu_match *dev_ctu, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_split_match: null context");
+  { std::string err; const int rc = match_args_check(n_pics, dev_out_a, dev_out_b, host_matches, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const size_t o_pics = 0, o_rec = up(o_pics + sizeof(MatchPic) * n_pics), o_ctu = up(o_rec + sizeof(fcu_pic_match) * n_pics),
+               total = dev_ctu ? o_ctu : up(o_ctu + sizeof(fcu_ctu_match) * (size_t)G.n_ctu * n_pics);
+  HIPCHK(c->maps.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->maps.p;
+  MatchPic *d_pics = (MatchPic *)(base + o_pics); fcu_pic_match *d_rec = (fcu_pic_match *)(base + o_rec);
+  fcu_ctu_match *d_ctu = dev_ctu ? dev_ctu : (fcu_ctu_match *)(base + o_ctu);
+  std::vector<MatchPic> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) { hp[i].a = dev_out_a[i]; hp[i].b = dev_out_b[i]; }
+  HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(MatchPic) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(match_ctu, dim3(G.n_ctu, n_pics), dim3(MAPS_THREADS), 0, st, d_pics, d_ctu, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  hipLaunchKernelGGL(match_pic, dim3(n_pics), dim3(MAPS_THREADS), 0, st, d_ctu, d_rec, G.n_ctu);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(2));
+  HIPCHK(hipMemcpyAsync(host_matches, d_rec, sizeof(fcu_pic_match) * n_pics, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and host_matches are done with */
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
+  return FCU_OK;
 }
 
 } /* extern "C" */

@@ -132,6 +132,43 @@ def hash_line(kind, string):
     return " [%s:%s]" % (HASH_LABELS[kind], string)
 
 
+class CtuMatch(C.Structure):
+    """fcu_ctu_match: the split match of one CTU."""
+    _fields_ = [("part_total", C.c_uint16), ("part_equal", C.c_uint16), ("node", ((C.c_uint16 * 2) * 2) * 4), ("only_a", C.c_uint16 * 4),
+                ("only_b", C.c_uint16 * 4), ("pad", C.c_uint16 * 6)]
+
+
+class PicMatch(C.Structure):
+    """fcu_pic_match: the sums over a picture's CTUs."""
+    _fields_ = [("part_total", C.c_uint64), ("part_equal", C.c_uint64), ("node", ((C.c_uint64 * 2) * 2) * 4), ("only_a", C.c_uint64 * 4),
+                ("only_b", C.c_uint64 * 4)]
+
+
+CTU_MATCH_DTYPE = np.dtype([("part_total", np.uint16), ("part_equal", np.uint16), ("node", np.uint16, (4, 2, 2)), ("only_a", np.uint16, (4,)),
+                            ("only_b", np.uint16, (4,)), ("pad", np.uint16, (6,))])                                                # fcu_ctu_match
+PIC_MATCH_DTYPE = np.dtype([("part_total", np.uint64), ("part_equal", np.uint64), ("node", np.uint64, (4, 2, 2)), ("only_a", np.uint64, (4,)),
+                            ("only_b", np.uint64, (4,))])                                                                          # fcu_pic_match
+# FCU_MAP_*: the byte-per-partition arrays of fcu_ctu_out a byte map can be taken from
+MAP_FIELDS = {n: i for i, n in enumerate(("depth", "part_size", "pred_mode", "skip", "merge_flag", "merge_idx", "tr_idx", "cbf_y", "cbf_cb", "cbf_cr",
+                                          "tskip_y", "tskip_cb", "tskip_cr", "intra_dir_luma", "intra_dir_chroma", "qp", "inter_dir", "mvp_idx", "ref_idx"))}
+MAP_SIGNED = ("part_size", "pred_mode", "qp", "mvp_idx", "ref_idx")      # int8 in the record: their maps come back as int8 views
+LABEL_ABSENT, LABEL_NOT_SPLIT, LABEL_SPLIT, LABEL_FORCED = -1, 0, 1, 2    # FCU_LABEL_*
+
+
+def pic_match_to_dict(rec):
+    """one element of a PIC_MATCH_DTYPE array -> dict: part_total, part_equal (int), node [4, 2, 2], only_a [4], only_b [4] (int64) and
+    split_match = part_equal / part_total, the share of the picture's 4x4 partitions decided to the same CU depth (bench.py's
+    figure of that name is stricter: it also asks for equal part_size and pred_mode, and walks all 256 entries of a cut CTU)"""
+    d = {n: (rec[n].astype(np.int64) if rec[n].ndim else int(rec[n])) for n in PIC_MATCH_DTYPE.names}
+    d["split_match"] = d["part_equal"] / d["part_total"] if d["part_total"] else 1.0
+    return d
+
+
+def map_level_shapes(width, height):
+    """[(BH(d), BW(d))] of the label / N_OBF maps of level d = 0..3 (blocks of 64 >> d samples)"""
+    return [((height + (64 >> d) - 1) // (64 >> d), (width + (64 >> d) - 1) // (64 >> d)) for d in range(4)]
+
+
 class VerifyCounts(C.Structure):
     """fcu_verify_counts: g_iVerResult[depth][TP, FP, TN, FN, FPLoss, FNLoss]."""
     _fields_ = [("n", (C.c_double * 6) * 4)]
@@ -145,7 +182,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
-           "fcu_picture_hash", "fcu_hash_string"]
+           "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -237,6 +274,8 @@ def load_lib():
     lib.fcu_picture_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_picture_hash.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_hash_string.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
+    lib.fcu_decision_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_split_match.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
     _lib = lib
     return lib
 
@@ -742,6 +781,90 @@ class CuEngine:
             d["line"] = {k: hash_string(hashes[i], k) for k in kinds}
             res.append(d)
         return (res, (ms[0], ms[1], ms[2])) if timed else res
+
+    # -- the decision as pictures
+    def _out_ptrs(self, pics, who):
+        ptrs = (C.c_void_p * max(len(pics), 1))()
+        for i, p in enumerate(pics):
+            o = p["out"] if isinstance(p, dict) else p
+            assert o.is_cuda and o.dtype == self.torch.uint8 and o.is_contiguous() and o.numel() >= self.n_ctu * CTU_OUT_BYTES, who
+            ptrs[i] = o.data_ptr()
+        return ptrs
+
+    def decision_maps(self, pics, fields=("depth",), mv=False, labels=False, obf=None, timed=False, stream=None):
+        """The decision of decided pictures as rasters aligned with the pixels, formed on the device (fcu_decision_maps).
+        pics: list of dicts with `out` (the result dicts of the drivers qualify) or of the fcu_ctu_out arrays themselves, uint8
+        device tensors.  fields: names among MAP_FIELDS, in the order wanted.  Returns a dict of device tensors over the batch
+        (n = len(pics), H4 = height / 4, W4 = width / 4):
+          one entry per field name   [n, H4, W4], uint8 or (MAP_SIGNED) int8: the array's bytes with z-order undone
+          "mv"      (mv=True)        int16 [n, H4, W4, 2], quarter samples [hor, ver]
+          "labels"  (labels=True)    four int8 tensors [n, ceil(height / s), ceil(width / s)], s = 64, 32, 16, 8: LABEL_* per block --
+                                     the split flags of the CUs on the chosen tree (at s = 8: NxN or not); LABEL_ABSENT where the
+                                     parent was not split, LABEL_FORCED where the picture edge forced the split
+          "n_obf"   (obf given)      four int16 tensors of those shapes: the fork's N_OBF feature of the block (values 0..256)
+        obf: the pictures' OBF maps from obf_prepass, an int16 tensor [n, H4, W4] or a list of [H4, W4] tensors.
+        timed=True: (dict, kernel ms).  The level tensors are views into one allocation per kind (rows of a picture are dense)."""
+        torch = self.torch
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        for f in fields:
+            if f not in MAP_FIELDS:
+                raise ValueError("decision_maps: fields are among %s, not %r" % (sorted(MAP_FIELDS), f))
+        n, H4, W4 = len(pics), self.height // 4, self.width // 4
+        dev = torch.device("cuda", self.device)
+        outs = self._out_ptrs(pics, "decision_maps")
+        shapes = map_level_shapes(self.width, self.height)
+        NL = sum(a * b for a, b in shapes)
+        ids = (C.c_int * max(len(fields), 1))(*[MAP_FIELDS[f] for f in fields])
+        d_bytes = torch.empty((n, len(fields), H4, W4), dtype=torch.uint8, device=dev) if fields else None
+        d_mv = torch.empty((n, H4, W4, 2), dtype=torch.int16, device=dev) if mv else None
+        d_lab = torch.empty((n, NL), dtype=torch.int8, device=dev) if labels else None
+        d_nobf, obf_ptrs, keep = None, None, None
+        if obf is not None:
+            keep = [obf[i] for i in range(n)]
+            assert len(obf) == n
+            for o in keep:
+                assert o.is_cuda and o.dtype == torch.int16 and o.is_contiguous() and tuple(o.shape) == (H4, W4)
+            obf_ptrs = (C.c_void_p * n)(*[o.data_ptr() for o in keep])
+            d_nobf = torch.empty((n, NL), dtype=torch.int16, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_decision_maps(self.h, n, outs, len(fields), ids, ptr(d_bytes), ptr(d_mv), ptr(d_lab), obf_ptrs, ptr(d_nobf),
+                                             C.byref(ms) if timed else None, s), "fcu_decision_maps")
+        res = {}
+        for k, f in enumerate(fields):
+            res[f] = d_bytes[:, k].view(torch.int8) if f in MAP_SIGNED else d_bytes[:, k]
+        if mv:
+            res["mv"] = d_mv
+        for name, t in (("labels", d_lab), ("n_obf", d_nobf)):
+            if t is not None:
+                res[name], o = [], 0
+                for bh, bw in shapes:
+                    res[name].append(t[:, o:o + bh * bw].unflatten(1, (bh, bw)))
+                    o += bh * bw
+        return (res, float(ms.value)) if timed else res
+
+    def split_match(self, pics_a, pics_b, ctu=False, timed=False, stream=None):
+        """How far two decisions of the same pictures agree, counted on the device (fcu_split_match): pics_a / pics_b as
+        decision_maps takes them, picture i of one against picture i of the other.  Returns one dict per picture
+        (pic_match_to_dict): part_total, part_equal (partitions of equal depth), split_match = their quotient, node[4][2][2]
+        (blocks that carry a coded split flag in both: by level, flag in A, flag in B), only_a[4], only_b[4] (a CU in one, absent
+        in the other).  ctu=True: also the per-CTU records, a structured array [n, n_ctu] of CTU_MATCH_DTYPE; timed=True: also the
+        durations (ms) of the two kernels.  The extras follow the list in that order."""
+        torch = self.torch
+        n = len(pics_a)
+        assert len(pics_b) == n
+        a, b = self._out_ptrs(pics_a, "split_match"), self._out_ptrs(pics_b, "split_match")
+        rec = np.zeros(max(n, 1), PIC_MATCH_DTYPE)
+        d_ctu = torch.empty((n, self.n_ctu, CTU_MATCH_DTYPE.itemsize), dtype=torch.uint8, device=torch.device("cuda", self.device)) if ctu else None
+        ms = (C.c_float * 2)() if timed else None
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_split_match(self.h, n, a, b, rec.ctypes.data, d_ctu.data_ptr() if ctu else None, ms, s), "fcu_split_match")
+        res = [pic_match_to_dict(rec[i]) for i in range(n)]
+        if not ctu and not timed:
+            return res
+        extra = ([d_ctu.cpu().numpy().view(CTU_MATCH_DTYPE).reshape(n, self.n_ctu)] if ctu else []) + ([(ms[0], ms[1])] if timed else [])
+        return (res, *extra)
 
     # -- TEncCu::destroy
     def destroy(self):

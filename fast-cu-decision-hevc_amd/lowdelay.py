@@ -37,6 +37,7 @@ import numpy as np
 
 from . import engine as _engine
 from .layout import PictureLayout
+from .sequence import engine_maps_options, split_batch_maps
 
 HM_LDP_RPS = {1: (-1, -5, -9, -13), 2: (-1, -2, -6, -10), 3: (-1, -3, -7, -11), 0: (-1, -4, -8, -12)}     # reference pictures of Frame1..Frame4 in encoder_lowdelay_P_main.cfg
 
@@ -58,7 +59,7 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
@@ -70,8 +71,12 @@ class LowDelayPDecider:
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
         statistics) of the final planes, taken on the device in one batched call for all clips.
         pic_hash="md5", "crc" or "checksum": every result dict gains `hash`, HM's decoded-picture hash string of the final planes
-        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call for all clips."""
+        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call for all clips.
+        maps=True, or a dict of CuEngine.decision_maps' keyword arguments (fields, mv, labels): every result dict gains `maps`, the
+        picture's raster maps as device tensors -- by default the depth, part-size, prediction-mode and ref_idx maps, the motion map
+        and the four split-label maps --, formed after the launch in one batched call for all clips."""
         self.do_report = report
+        self.maps = engine_maps_options(maps, ("depth", "part_size", "pred_mode", "ref_idx"), "LowDelayPDecider", mv=True)
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("LowDelayPDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
         self.pic_hash = pic_hash
@@ -146,6 +151,9 @@ class LowDelayPDecider:
         if self.pic_hash:                                    # on the final planes as well, nothing but the digests comes back
             for r, d in zip(res, eng.picture_hash(res, kinds=(self.pic_hash,))):
                 r["hash"] = d["line"][self.pic_hash]
+        if self.maps:
+            for r, m in zip(res, split_batch_maps(eng.decision_maps(res, **self.maps), len(res))):
+                r["maps"] = m
         for s, r in enumerate(res):
             self.col[s] = r["out"]                           # stays in HBM: the next picture's collocated motion field
             self.ref[s] = eng.pad_reference(r["rec"])          # reference of the next picture of this clip

@@ -75,11 +75,28 @@ def write_yuv420(f, planes):
         f.write(np.ascontiguousarray(p, np.uint8).tobytes())
 
 
+def engine_maps_options(maps, default_fields, who, mv=False):
+    """the maps= option of the drivers -> keyword arguments of CuEngine.decision_maps, or None"""
+    if maps is None or maps is False:
+        return None
+    opt = {"fields": default_fields, "mv": mv, "labels": True}
+    if maps is not True:
+        if not isinstance(maps, dict) or set(maps) - {"fields", "mv", "labels"}:
+            raise ValueError(who + ": maps is None, True or a dict with fields / mv / labels")
+        opt.update(maps)
+    return opt
+
+
+def split_batch_maps(res, n):
+    """the batch tensors of CuEngine.decision_maps -> one dict per picture (views)"""
+    return [{k: ([t[i] for t in v] if isinstance(v, list) else v[i]) for k, v in res.items()} for i in range(n)]
+
+
 class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -97,8 +114,13 @@ class SequenceDecider:
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
         statistics) of the final planes, taken on the device in one batched call for the pictures of a group.
         pic_hash="md5", "crc" or "checksum": every result dict gains `hash`, HM's decoded-picture hash string of the final planes
-        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call per group."""
+        (CuEngine.picture_hash; what the encoder prints as [MD5:...] / [CRC:...] / [Checksum:...]), one batched call per group.
+        maps=True, or a dict of CuEngine.decision_maps' keyword arguments (fields, mv, labels): every result dict gains `maps`, the
+        picture's raster maps as device tensors -- by default the depth, part-size, prediction-mode and luma-mode maps and the four
+        split-label maps; a picture that was decided with an OBF map (fast=True, outside Training) also gets `n_obf`.  They are
+        formed after the launch, one batched call per group."""
         self.do_report = report
+        self.maps = engine_maps_options(maps, ("depth", "part_size", "pred_mode", "intra_dir_luma"), "SequenceDecider")
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
         self.pic_hash = pic_hash
@@ -144,6 +166,8 @@ class SequenceDecider:
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
+            if self.maps and state != TRAINING:
+                pics[-1]["obf"] = obf
         eng.compress_pictures(0, len(yuvs), self.layout)
         nb = _engine.CTU_OUT_BYTES
         for p in pics:
@@ -158,6 +182,10 @@ class SequenceDecider:
         if self.pic_hash:                                    # on the final planes as well, nothing but the digests comes back
             for p, d in zip(pics, eng.picture_hash(pics, kinds=(self.pic_hash,))):
                 p["hash"] = d["line"][self.pic_hash]
+        if self.maps:                                        # the pictures of a group share their state: all of them have an OBF map or none
+            obf = [p.pop("obf") for p in pics] if "obf" in pics[0] else None
+            for p, m in zip(pics, split_batch_maps(eng.decision_maps(pics, obf=obf, **self.maps), len(pics))):
+                p["maps"] = m
         eng.sync()
         for p in pics:
             p["depth"] = p["out"].view(eng.n_ctu, nb)[:, :256].cpu().numpy().copy()      # fcu_ctu_out.depth leads the struct

@@ -43,6 +43,10 @@
  *   calcMD5 / calcCRC / calcChecksum,               fcu_picture_hash (the decoded-picture hash of reconstructed pictures, per
  *     digestToString (TComPicYuvMD5.cpp:44-225,       plane, as the encoder prints it at the end of the picture line),
  *      TEncGOP.cpp:1619-1640,1742-1756)               fcu_hash_string (the printed form)
+ *   the published decision as pictures;             fcu_decision_maps (raster maps of the per-partition arrays of fcu_ctu_out, the
+ *     the fork's Training dump of split labels         motion map, per-CU split labels and N_OBF features of the chosen tree),
+ *     next to N_OBF (tools_YS.cpp:304-318,             fcu_split_match (agreement of two decisions of a picture, per partition
+ *      TEncCu.cpp:585-600,1489-1497)                   and per quadtree node)
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -439,6 +443,59 @@ int  fcu_picture_hash(fcu_ctx *c, int n_pics, int kinds, const uint8_t *const *d
  * short for the string and its terminator (MD5 needs 99 bytes). */
 int  fcu_hash_string(const fcu_pic_hash *h, int kind, char *buf, int buf_len);
 
+/* ---- decision maps: the decision of whole pictures as rasters aligned with the pixels, formed where the records lie, in HBM.
+ * With W4 = width / 4, H4 = height / 4 and, for level d = 0..3 of the quadtree, s = 64 >> d, BW(d) = ceil(width / s),
+ * BH(d) = ceil(height / s), NL = sum over d of BW(d) * BH(d):
+ *   byte maps     uint8 [n_pics][n_fields][H4][W4]: entry (y4, x4) of map k is the byte fcu_ctu_out.<field_ids[k]> holds for the
+ *                 4x4 partition at luma (4 x4, 4 y4) -- z-order undone; signed fields (part_size, pred_mode, qp, mvp_idx, ref_idx)
+ *                 keep their byte.  Only the arrays named are read.
+ *   motion map    int16 [n_pics][H4][W4][2] from fcu_ctu_out.mv ([hor, ver], quarter samples)
+ *   label maps    int8 [n_pics][NL]: per picture the four levels one after the other, level d as [BH(d)][BW(d)] at element offset
+ *                 sum over e < d of BW(e) * BH(e).  Entry (by, bx) of level d describes the s x s block at luma (bx s, by s), from
+ *                 depth (and, at d = 3, part_size) of the block's top-left partition -- an FCU_LABEL_* code.  These are the split
+ *                 flags of the CUs ON THE CHOSEN TREE (what TEncCu::xEncodeCU codes, TEncCu.cpp:1679-1699; at d = 3 the choice
+ *                 SIZE_NxN of the 8x8 CU).  The fork's Training dump (tools_YS.cpp:304-318, written at TEncCu.cpp:1489-1497) also
+ *                 labels the CUs its exhaustive search visited and discarded; those are not in fcu_ctu_out and get no label.
+ *   N_OBF maps    uint16 [n_pics][NL], the layout of the label maps: the fork's feature of that block (TEncCu.cpp:585-600) -- the
+ *                 number of 4x4 blocks of the block's area inside the picture whose count in the OBF map of fcu_obf_prepass is > 0.
+ * Entries of a record that belong to partitions outside the picture reach no output. */
+enum { FCU_MAP_DEPTH = 0, FCU_MAP_PART_SIZE, FCU_MAP_PRED_MODE, FCU_MAP_SKIP, FCU_MAP_MERGE_FLAG, FCU_MAP_MERGE_IDX, FCU_MAP_TR_IDX,
+       FCU_MAP_CBF_Y, FCU_MAP_CBF_CB, FCU_MAP_CBF_CR, FCU_MAP_TSKIP_Y, FCU_MAP_TSKIP_CB, FCU_MAP_TSKIP_CR, FCU_MAP_INTRA_DIR_LUMA,
+       FCU_MAP_INTRA_DIR_CHROMA, FCU_MAP_QP, FCU_MAP_INTER_DIR, FCU_MAP_MVP_IDX, FCU_MAP_REF_IDX, FCU_MAP_FIELDS };
+enum { FCU_LABEL_ABSENT = -1,      /* depth < d: the parent was not split, there is no CU of this size here                       */
+       FCU_LABEL_NOT_SPLIT = 0,    /* a CU of depth d that was not split (split_cu_flag 0); at d = 3: part_size is not NxN        */
+       FCU_LABEL_SPLIT = 1,        /* depth > d (split_cu_flag 1); at d = 3: part_size NxN                                       */
+       FCU_LABEL_FORCED = 2 };     /* d < 3 and the block does not lie wholly inside the picture: split without a coded flag
+                                      (bBoundary, TEncCu.cpp:486-488,1694-1699); the fork never labels these CUs                             */
+/* Maps of n_pics decided pictures of this context's size.  dev_out: host array of n_pics device pointers, each picture's fcu_ctu_out
+ * array.  field_ids: n_fields distinct FCU_MAP_* ids, in the order of the maps (n_fields 0: no byte maps).  dev_bytes, dev_mv,
+ * dev_labels, dev_nobf: device outputs of the shapes above, NULL = not wanted; dev_bytes may start at any byte (rows go out as 16-byte
+ * units when W4 is a multiple of 16 and the base is 16-byte aligned, else as 2-byte units), dev_mv and dev_nobf at any even byte.
+ * dev_obf: host array of n_pics device pointers, each picture's OBF map (int16 [H4][W4] of fcu_obf_prepass); given exactly when dev_nobf
+ * is.  Nothing is modified but the outputs; every output byte is written by exactly one thread, no atomics and no buffer that must be
+ * cleared: the same input gives the same bytes.  One kernel on `hip_stream`; the call returns after it has finished; kernel_ms (may be
+ * NULL) receives its duration.
+ * FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1; a NULL dev_out or entry of it; n_fields outside
+ * 0..FCU_MAP_FIELDS; n_fields > 0 with a NULL field_ids or a NULL dev_bytes, and dev_bytes with n_fields 0; an unknown or repeated
+ * field id; dev_nobf without dev_obf and the reverse, a NULL entry of dev_obf; no output wanted at all.  No CPU fallback. */
+int  fcu_decision_maps(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out, int n_fields, const int *field_ids,
+                       uint8_t *dev_bytes, int16_t *dev_mv, int8_t *dev_labels, const int16_t *const *dev_obf, uint16_t *dev_nobf,
+                       float *kernel_ms, void *hip_stream);
+/* ---- split match: how far two decisions A and B of the same picture agree (a Testing-state picture against its exhaustive
+ * decision).  part_total = 4x4 partitions inside the picture; part_equal = those whose depth is equal
+ * in A and B; node[d][a][b] = blocks of level d that are a CU with a coded flag in both (label a in A, b in B; 0 = not split,
+ * 1 = split: the diagonal agrees); only_a[d] / only_b[d] = blocks that are such a CU in one decision and absent in the other.
+ * Forced blocks (FCU_LABEL_FORCED) are counted nowhere.  Neither structure has implicit padding. */
+typedef struct fcu_ctu_match { uint16_t part_total, part_equal, node[4][2][2], only_a[4], only_b[4], pad[6]; } fcu_ctu_match;   /* 64 B */
+typedef struct fcu_pic_match { uint64_t part_total, part_equal, node[4][2][2], only_a[4], only_b[4]; } fcu_pic_match;           /* 208 B */
+/* dev_out_a / dev_out_b: host arrays of n_pics device pointers to fcu_ctu_out arrays (only depth and part_size are read);
+ * host_matches receives n_pics records; dev_ctu (device, [n_pics][fcu_num_ctus], or NULL: a buffer of the context) the per-CTU
+ * records.  Two kernels on `hip_stream` (one record per CTU, then 64-bit sums per picture); no atomics, nothing to clear; the call
+ * returns after they have finished; kernel_ms2 (may be NULL) receives their durations.  FCU_ERR_ARG: n_pics < 1, a NULL array, a NULL
+ * entry of one, NULL host_matches. */
+int  fcu_split_match(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b,
+                     fcu_pic_match *host_matches, fcu_ctu_match *dev_ctu, float *kernel_ms2, void *hip_stream);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -474,7 +531,7 @@ const char *fcu_build_info(void);
  * in another language (ctypes, cgo, JNI) checks its own layouts against them before the first call; tests/test_cabi.py does. */
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
        FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9,
-       FCU_ABI_PIC_HASH = 10 };
+       FCU_ABI_PIC_HASH = 10, FCU_ABI_CTU_MATCH = 11, FCU_ABI_PIC_MATCH = 12 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus

@@ -22,6 +22,11 @@ intra / skipped / merged area; the reconstruction is then copied to the host onl
 --hash md5|crc|checksum appends the decoded-picture hash of the reconstruction to the picture line exactly as the reference encoder
 prints it with SEIDecodedPictureHash 1 / 2 / 3 (` [MD5:...]`, ` [CRC:...]`, ` [Checksum:...]`, TEncGOP.cpp:1746-1754), taken on the
 device (fcu_picture_hash): with --report --hash and no --rec no plane is copied to the host.
+--maps FILE.npz saves the decision as pictures, formed on the device (fcu_decision_maps): `depth`, `part_size`, `pred_mode` and
+`intra_dir_luma` as arrays [pictures, height / 4, width / 4] aligned with the pixels, and `label0` .. `label3`, the split labels per
+64x64 .. 8x8 block ([pictures, ceil(height / s), ceil(width / s)]; -1 absent, 0 not split, 1 split, 2 split forced by the picture edge).
+With --fast it also holds `n_obf0` .. `n_obf3`, the fork's N_OBF feature of the same blocks, for the pictures decided with an OBF map
+(Verifying and Testing), and `n_obf_poc`, the POCs of those pictures.
 """
 import argparse
 import os
@@ -58,6 +63,7 @@ def main():
     ap.add_argument("--hash", choices=("md5", "crc", "checksum"), default=None, help="append HM's decoded-picture hash of the reconstruction to the picture line, taken on the device")
     ap.add_argument("--rec")
     ap.add_argument("--depth")
+    ap.add_argument("--maps", metavar="FILE.npz", help="save the raster depth, part-size, prediction-mode and luma-mode maps and the split-label maps of every picture (with --fast: the N_OBF maps as well)")
     args = ap.parse_args()
     tiles = None
     if args.tiles is not None:
@@ -71,13 +77,14 @@ def main():
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
-        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report, pic_hash=args.hash,
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report, pic_hash=args.hash, maps=True if args.maps else None,
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
     depths = []
+    maps = {}
     n = 0
     t_all = time.perf_counter()
     while n < args.frames:
@@ -115,6 +122,16 @@ def main():
                 seq.write_yuv420(rec_f, [p.cpu().numpy() for p in r["rec"]])
             if args.depth:
                 depths.append(r["depth"])
+            if args.maps:
+                m = r["maps"]
+                for k in ("depth", "part_size", "pred_mode", "intra_dir_luma"):
+                    maps.setdefault(k, []).append(m[k].cpu().numpy())
+                for d in range(4):
+                    maps.setdefault("label%d" % d, []).append(m["labels"][d].cpu().numpy())
+                    if "n_obf" in m:
+                        maps.setdefault("n_obf%d" % d, []).append(m["n_obf"][d].cpu().numpy().astype(np.uint16))
+                if "n_obf" in m:
+                    maps.setdefault("n_obf_poc", []).append(np.int32(r["poc"]))
         print(f"  {len(res)} picture(s) side by side: {dt * 1e3:.1f} ms", flush=True)
         n += len(res)
     dt_all = time.perf_counter() - t_all
@@ -122,6 +139,8 @@ def main():
         rec_f.close()
     if args.depth:
         np.save(args.depth, np.stack(depths) if depths else np.zeros((0, 0, 256), np.uint8))
+    if args.maps:
+        np.savez(args.maps, **{k: np.stack(v) for k, v in maps.items()})
     dec.close()
     print(f"{n} pictures decided in {dt_all:.2f} s")
 
