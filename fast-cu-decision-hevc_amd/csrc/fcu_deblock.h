@@ -19,10 +19,15 @@
  * edge with a coded luma block on either side, or across different motion (P slices: one list; |dmv| >= 4 quarter samples
  * or different reference); else 0.  Chroma is filtered at Bs 2 only.
  * Algorithmic bytes per pass: read 1.5*W*H samples + 4 bytes of CU data per 4x4 partition, write <= 1.5*W*H.
- * Tiles: dbk_pass<DIR> (TILES = false) is the filter of LFCrossTileBoundaryFlag 1 (a tile boundary is an edge like any other
- * CTU boundary); dbk_pass<DIR, true> is the compile-time variant that takes the tile grid (LfTiles, fcu_host.h) by value and,
- * with the flag 0, drops the edges that lie on a tile boundary (:379,401,430-434,609-613,754-758) exactly as the picture
+ * Tiles: dbk_pass<DIR> (CUT = LF_CUT_NONE) is the filter of LFCrossTileBoundaryFlag 1 (a tile boundary is an edge like any other
+ * CTU boundary); dbk_pass<DIR, LF_CUT_TILES> is the compile-time variant that takes the tile grid (LfTiles, fcu_host.h) by value
+ * and, with the flag 0, drops the edges that lie on a tile boundary (:379,401,430-434,609-613,754-758) exactly as the picture
  * border is dropped.  The variant without tiles compiles to the instructions it had before the grid existed.
+ * Slices: dbk_pass<DIR> is also the filter of LFCrossSliceBoundaryFlag 1.  dbk_pass<DIR, LF_CUT_SLICES> is the filter of the
+ * flag 0 (fcu_deblock_slices): it takes the slice length (LfSlices) by value, and a partition on the left / top edge of its CTU
+ * gets no edge flag when the CTU to the left / above lies in another slice (:369-411 with getPULeft / getPUAbove,
+ * TComDataCU.cpp:1095,1134; :430-434,609-613,754-758) -- as on the picture border, luma and chroma.  With S CTUs per slice and
+ * r = a % S of the CTU's raster address a, the left CTU is in another slice iff r == 0 and the CTU above iff r < w_ctu.
  */
 #pragma once
 
@@ -38,10 +43,10 @@ enum { DBK_THREADS = 256 };
 __device__ static inline int dbk_clip3(int lo, int hi, int v) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ static inline int dbk_abs(int v) { return v < 0 ? -v : v; }
 
-/* (TILES does nothing in the helpers below: it gives each kernel variant its own copy, so that the kernels without a grid see
+/* (CUT does nothing in the helpers below: it gives each kernel variant its own copy, so that the kernels without a grid see
  * the call graph they had -- one caller per helper and direction -- and come out of the inliner as they did) */
 /* one line across a luma edge, xPelFilterLuma (:805-869): m[0..3] = P side (m[3] next to the edge), m[4..7] = Q side */
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline void dbk_line_luma(int m[8], int tc, int sw, int thrCut, int filtP, int filtQ)
 {
   const int m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5], m6 = m[6], m7 = m[7];
@@ -65,7 +70,7 @@ __device__ static inline void dbk_line_luma(int m[8], int tc, int sw, int thrCut
   }
 }
 /* the four lines of one luma segment: the loop body of xEdgeFilterLuma (:597-665).  Returns 0 when nothing is filtered. */
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline int dbk_segment_luma(int m[4][8], int qp, int betaOff, int tcOff, int bs)
 {
   const int tc = k_dbk_tc[dbk_clip3(0, 53, qp + 2 * (bs - 1) + tcOff * 2)];           /* + DEFAULT_INTRA_TC_OFFSET * (Bs - 1) */
@@ -81,11 +86,11 @@ __device__ static inline int dbk_segment_luma(int m[4][8], int qp, int betaOff, 
   const int s3 = (dbk_abs(m[3][0] - m[3][3]) + dbk_abs(m[3][7] - m[3][4]) < (beta >> 3)) && (2 * d3 < (beta >> 2)) && (dbk_abs(m[3][3] - m[3][4]) < ((tc * 5 + 1) >> 1));
   const int sw = s0 && s3;
 #pragma unroll
-  for (int i = 0; i < 4; i++) dbk_line_luma<TILES>(m[i], tc, sw, thrCut, filtP, filtQ);
+  for (int i = 0; i < 4; i++) dbk_line_luma<CUT>(m[i], tc, sw, thrCut, filtP, filtQ);
   return 1;
 }
 /* xPelFilterChroma (:881-905): c = { m2, m3 | m4, m5 } */
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline void dbk_line_chroma(int c[4], int tc)
 {
   const int delta = dbk_clip3(-tc, tc, ((((c[2] - c[1]) * 4) + c[0] - c[3] + 4) >> 3));
@@ -105,11 +110,12 @@ __device__ static inline int dbk_zidx(int x4, int y4)
 struct DbkPart { int flag, qp, bs; };
 /* CU data of the partition (x4, y4) (4-sample units of the picture) for direction DIR: is its left / top border a
  * filtered edge, and its QP */
-/* the grid argument of a kernel variant: nothing without tiles, LfTiles (fcu_host.h) with them */
-template <bool TILES> struct DbkGrid { };
-template <> struct DbkGrid<true> { LfTiles t; };
-template <int DIR, bool TILES = false>
-__device__ static inline DbkPart dbk_part(const fcu_ctu_out *out, int w_ctu, int x4, int y4, const DbkGrid<TILES> &T = DbkGrid<TILES>())
+/* the grid argument of a kernel variant: nothing without tiles, LfTiles (fcu_host.h) with them, LfSlices for slices */
+template <int CUT> struct DbkGrid { };
+template <> struct DbkGrid<LF_CUT_TILES> { LfTiles t; };
+template <> struct DbkGrid<LF_CUT_SLICES> { LfSlices s; };
+template <int DIR, int CUT = LF_CUT_NONE>
+__device__ static inline DbkPart dbk_part(const fcu_ctu_out *out, int w_ctu, int x4, int y4, const DbkGrid<CUT> &T = DbkGrid<CUT>())
 {
   const fcu_ctu_out *c = &out[(y4 >> 4) * w_ctu + (x4 >> 4)];
   const int z = dbk_zidx(x4, y4);
@@ -119,7 +125,13 @@ __device__ static inline DbkPart dbk_part(const fcu_ctu_out *out, int w_ctu, int
   const int cu = CTU >> c->depth[z], tu = cu >> c->tr_idx[z], ps = c->part_size[z];
   r.flag = 0; r.bs = 0;
   if (ps == SIZE_NONE || pos == 0) return r;
-  if constexpr (TILES) { if (!T.t.cross && (pos & 63) == 0 && lf_tile_start(DIR == 0 ? T.t.col : T.t.row, pos >> 6)) return r; }      /* a tile boundary, LFCrossTileBoundaryFlag 0: as the picture border */
+  if constexpr (CUT == LF_CUT_TILES) { if (!T.t.cross && (pos & 63) == 0 && lf_tile_start(DIR == 0 ? T.t.col : T.t.row, pos >> 6)) return r; }      /* a tile boundary, LFCrossTileBoundaryFlag 0: as the picture border */
+  if constexpr (CUT == LF_CUT_SLICES) {                                      /* a slice boundary, LFCrossSliceBoundaryFlag 0: as the picture border */
+    if ((pos & 63) == 0) {                                                   /* only a partition on its CTU's edge looks at another CTU: one remainder */
+      const unsigned rem = (unsigned)((y4 >> 4) * w_ctu + (x4 >> 4)) % (unsigned)T.s.slice_ctus;
+      if (DIR == 0 ? rem == 0 : rem < (unsigned)w_ctu) return r;
+    }
+  }
   if ((pos & (tu - 1)) == 0) r.flag = 1;                                   /* transform-unit / CU edge */
   else if ((pos & (cu - 1)) == (cu >> 1) && (ps == SIZE_NxN || (DIR == 0 ? ps == SIZE_Nx2N : ps == SIZE_2NxN))) r.flag = 2;   /* PU edge only */
   /* asymmetric partitions: the edge at a quarter of the CU (xSetEdgefilterPU, TComLoopFilter.cpp:331-350); only 32x32 and
@@ -138,16 +150,17 @@ __device__ static inline DbkPart dbk_part(const fcu_ctu_out *out, int w_ctu, int
   r.bs = ((rp < 0) != (rq < 0) || (rp >= 0 && rp != rq) || dbk_abs(mqx - mpx) >= 4 || dbk_abs(mqy - mpy) >= 4) ? 1 : 0;
   return r;
 }
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline int dbk_qp_of(const fcu_ctu_out *out, int w_ctu, int x4, int y4)
 {
   return out[(y4 >> 4) * w_ctu + (x4 >> 4)].qp[dbk_zidx(x4, y4)];
 }
 
-/* TILES = false: the kernel fcu_deblock launches (an empty grid argument); TILES = true: fcu_deblock_tiles, the grid by value */
-template <int DIR, bool TILES = false>
+/* CUT = LF_CUT_NONE: the kernel fcu_deblock launches (an empty grid argument); LF_CUT_TILES: fcu_deblock_tiles, the grid by value;
+ * LF_CUT_SLICES: fcu_deblock_slices with LFCrossSliceBoundaryFlag 0 and more than one slice, the slice length by value */
+template <int DIR, int CUT = LF_CUT_NONE>
 __global__ void __launch_bounds__(DBK_THREADS)
-dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int h, int w_ctu, int betaOff, int tcOff, DbkGrid<TILES> T = DbkGrid<TILES>())
+dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int h, int w_ctu, int betaOff, int tcOff, DbkGrid<CUT> T = DbkGrid<CUT>())
 {
   const int id = (int)(blockIdx.x * DBK_THREADS + threadIdx.x);
   const int cw = w >> 1;
@@ -155,9 +168,9 @@ dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int 
     const int ne = w >> 3, x8 = id % ne, y4 = id / ne;
     if (y4 >= (h >> 2)) return;
     const int x4 = x8 * 2;
-    const DbkPart q = dbk_part<0, TILES>(out, w_ctu, x4, y4, T);
+    const DbkPart q = dbk_part<0, CUT>(out, w_ctu, x4, y4, T);
     if (!q.bs) return;                                         /* no edge here (incl. the picture border x = 0, :358-365) or Bs 0 */
-    const int qp = (dbk_qp_of<TILES>(out, w_ctu, x4 - 1, y4) + q.qp + 1) >> 1;
+    const int qp = (dbk_qp_of<CUT>(out, w_ctu, x4 - 1, y4) + q.qp + 1) >> 1;
     int m[4][8];
     uint8_t *p = Y + (size_t)(y4 * 4) * w + x4 * 4 - 4;
 #pragma unroll
@@ -166,7 +179,7 @@ dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int 
 #pragma unroll
       for (int k = 0; k < 4; k++) { m[i][k] = (a >> (8 * k)) & 255; m[i][4 + k] = (b >> (8 * k)) & 255; }
     }
-    if (dbk_segment_luma<TILES>(m, qp, betaOff, tcOff, q.bs)) {
+    if (dbk_segment_luma<CUT>(m, qp, betaOff, tcOff, q.bs)) {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         *(uint32_t *)(p + (size_t)i * w) = (uint32_t)m[i][0] | ((uint32_t)m[i][1] << 8) | ((uint32_t)m[i][2] << 16) | ((uint32_t)m[i][3] << 24);
@@ -182,7 +195,7 @@ dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int 
         for (int i = 0; i < 2; i++) {
           const uint32_t a = *(const uint16_t *)(cp + (size_t)i * cw), b = *(const uint16_t *)(cp + (size_t)i * cw + 2);
           int c[4] = { (int)(a & 255), (int)(a >> 8), (int)(b & 255), (int)(b >> 8) };
-          dbk_line_chroma<TILES>(c, tc);
+          dbk_line_chroma<CUT>(c, tc);
           cp[(size_t)i * cw + 1] = (uint8_t)c[1]; cp[(size_t)i * cw + 2] = (uint8_t)c[2];
         }
       }
@@ -197,16 +210,16 @@ dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int 
     uint32_t ra[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) ra[k] = *(const uint32_t *)(p + (size_t)k * w);
-    const DbkPart q = dbk_part<1, TILES>(out, w_ctu, x4, y4, T);
+    const DbkPart q = dbk_part<1, CUT>(out, w_ctu, x4, y4, T);
     if (!q.bs) return;
-    const int qp = (dbk_qp_of<TILES>(out, w_ctu, x4, y4 - 1) + q.qp + 1) >> 1;
+    const int qp = (dbk_qp_of<CUT>(out, w_ctu, x4, y4 - 1) + q.qp + 1) >> 1;
     int m[4][8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
 #pragma unroll
       for (int i = 0; i < 4; i++) m[i][k] = (ra[k] >> (8 * i)) & 255;
     }
-    if (dbk_segment_luma<TILES>(m, qp, betaOff, tcOff, q.bs)) {
+    if (dbk_segment_luma<CUT>(m, qp, betaOff, tcOff, q.bs)) {
 #pragma unroll
       for (int k = 1; k < 7; k++)
         *(uint32_t *)(p + (size_t)k * w) = (uint32_t)m[0][k] | ((uint32_t)m[1][k] << 8) | ((uint32_t)m[2][k] << 16) | ((uint32_t)m[3][k] << 24);
@@ -222,7 +235,7 @@ dbk_pass(const fcu_ctu_out *out, uint8_t *Y, uint8_t *U, uint8_t *V, int w, int 
 #pragma unroll
         for (int i = 0; i < 2; i++) {
           int c[4] = { (int)((r[0] >> (8 * i)) & 255), (int)((r[1] >> (8 * i)) & 255), (int)((r[2] >> (8 * i)) & 255), (int)((r[3] >> (8 * i)) & 255) };
-          dbk_line_chroma<TILES>(c, tc);
+          dbk_line_chroma<CUT>(c, tc);
           cp[(size_t)1 * cw + i] = (uint8_t)c[1]; cp[(size_t)2 * cw + i] = (uint8_t)c[2];
         }
       }

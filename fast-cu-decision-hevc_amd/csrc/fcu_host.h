@@ -231,6 +231,23 @@ FCU_DEV int lf_tile_start(const uint64_t *m, int i)
   return (int)((w >> (i & 63)) & 1u);
 }
 
+/* ---- what cuts the picture for a loop-filter kernel: the compile-time variant (the template argument CUT of fcu_deblock.h and
+ * fcu_sao.h).  LF_CUT_TILES is 1: the variants with tiles used to be `true` of a bool. */
+enum { LF_CUT_NONE = 0, LF_CUT_TILES = 1, LF_CUT_SLICES = 2 };
+/* ---- the slices as the loop-filter kernels take them (fcu_deblock_slices / fcu_sao_slices) with LFCrossSliceBoundaryFlag 0.
+ * A slice is slice_ctus consecutive CTUs in raster order, the last one what is left, so the length is the whole description: no
+ * table and no limit on the picture.  CTU a lies in [a - a % S, min(a - a % S + S, n_ctu)). */
+struct LfSlices { int32_t slice_ctus; };
+/* CTUs per slice as the filters count them: 0, or the picture's CTU count and more, is one slice */
+inline int lf_slice_len(int n_ctu, int slice_ctus) { return slice_ctus <= 0 || slice_ctus > n_ctu ? n_ctu : slice_ctus; }
+/* true = the slice variants run (S filled in); false = LFCrossSliceBoundaryFlag 1 or one slice: the picture filters as
+ * fcu_deblock / fcu_sao filter it, by their kernels */
+inline bool lf_slices_fill(LfSlices &S, int n_ctu, int slice_ctus, int cross)
+{
+  S.slice_ctus = lf_slice_len(n_ctu, slice_ctus);
+  return cross == 0 && S.slice_ctus < n_ctu;
+}
+
 /* PSNR of a plane of n 8-bit samples from its sum of squared differences, as TEncGOP::xCalculateAddPSNR prints it
  * (TEncGOP.cpp:2254-2256): the reference value 255 * 255 * n in double precision, 999.99 for an exact reconstruction */
 inline double report_psnr(uint64_t ssd, uint64_t n)

@@ -609,8 +609,16 @@ static int lf_tiles_arg(const fcu_ctx *c, int n_cols, int n_rows, int lf_cross_t
   return FCU_OK;
 }
 
-/* fcu_deblock (T null: the kernels without a grid) and fcu_deblock_tiles */
-static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+/* the slices of fcu_deblock_slices / fcu_sao_slices; FCU_ERR_ARG with the entry point's name */
+static int lf_slices_arg(int slice_ctus, int lf_cross_slices, const char *name)
+{
+  if (lf_cross_slices != 0 && lf_cross_slices != 1) return fail(FCU_ERR_ARG, std::string(name) + ": lf_cross_slices (LFCrossSliceBoundaryFlag) is 0 or 1");
+  if (slice_ctus < 0) return fail(FCU_ERR_ARG, std::string(name) + ": slice_ctus must not be negative (0 = one slice per picture)");
+  return FCU_OK;
+}
+
+/* fcu_deblock (T and S null: the kernels without a grid), fcu_deblock_tiles (T) and fcu_deblock_slices (S, where the slices cut) */
+static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const LfSlices *S, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
                        int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream)
 {
   if (!dev_out || !dev_rec_y || !dev_rec_u || !dev_rec_v) return fail(FCU_ERR_ARG, std::string(name) + ": bad argument");
@@ -623,12 +631,14 @@ static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const fcu
   HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
   /* all vertical edges of the picture before the first horizontal one (TComLoopFilter.cpp:133-154): stream order */
   const dim3 g0((n0 + DBK_THREADS - 1) / DBK_THREADS), g1((n1 + DBK_THREADS - 1) / DBK_THREADS);
-  if (T) hipLaunchKernelGGL((dbk_pass<0, true>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
-  else hipLaunchKernelGGL((dbk_pass<0, false>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
+  if (T) hipLaunchKernelGGL((dbk_pass<0, LF_CUT_TILES>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_TILES>{ *T });
+  else if (S) hipLaunchKernelGGL((dbk_pass<0, LF_CUT_SLICES>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_SLICES>{ *S });
+  else hipLaunchKernelGGL((dbk_pass<0, LF_CUT_NONE>), g0, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_NONE>());
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(1));
-  if (T) hipLaunchKernelGGL((dbk_pass<1, true>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<true>{ *T });
-  else hipLaunchKernelGGL((dbk_pass<1, false>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<false>());
+  if (T) hipLaunchKernelGGL((dbk_pass<1, LF_CUT_TILES>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_TILES>{ *T });
+  else if (S) hipLaunchKernelGGL((dbk_pass<1, LF_CUT_SLICES>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_SLICES>{ *S });
+  else hipLaunchKernelGGL((dbk_pass<1, LF_CUT_NONE>), g1, dim3(DBK_THREADS), 0, st, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, w, h, w_ctu, beta_offset_div2, tc_offset_div2, DbkGrid<LF_CUT_NONE>());
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(2));
   if (kernel_ms2) { HIPCHK(hipStreamSynchronize(st)); ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
@@ -636,8 +646,9 @@ static int deblock_run(fcu_ctx *c, const char *name, const LfTiles *T, const fcu
 }
 
 static size_t up(size_t v) { return (v + 255) & ~(size_t)255; }      /* sub-blocks of a DevBuf start at multiples of 256 bytes */
-/* fcu_sao (T null: the kernels without a grid) and fcu_sao_tiles */
-static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
+/* fcu_sao (T null, no_cross_slices false: the kernels without a grid), fcu_sao_tiles (T) and fcu_sao_slices (no_cross_slices =
+ * LFCrossSliceBoundaryFlag 0: the slice variants of the statistics and the offset pass, where a picture of the batch has slices) */
+static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, bool no_cross_slices, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
                    fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
 {
   const std::string name(name_);
@@ -652,6 +663,8 @@ static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, 
   HIPCHK(hipSetDevice(c->hs.sp.device));
   hipStream_t st = (hipStream_t)hip_stream;
   const int w = c->hs.sp.width, h = c->hs.sp.height, w_ctu = c->hs.w_ctu, n_ctu = c->hs.n_ctu;
+  bool SL = false;                                           /* one slice in every picture: nothing to cut, the plain kernels */
+  for (int i = 0; i < n_pics && no_cross_slices; i++) { LfSlices S; SL = SL || lf_slices_fill(S, n_ctu, params[i].slice_ctus, 0); }
   if (w_ctu + 1 > SAO_RING) return fail(FCU_ERR_ARG, name + ": pictures wider than 255 CTUs are not supported (sao_decide's neighbour ring)");
   const size_t plane[3] = { (size_t)w * h, (size_t)(w / 2) * (h / 2), (size_t)(w / 2) * (h / 2) }, pic_bytes = plane[0] + 2 * plane[1];
   const size_t o_pics = 0, o_src = up(o_pics + sizeof(SaoPic) * n_pics), o_stats = up(o_src + pic_bytes * n_pics),
@@ -680,6 +693,7 @@ static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, 
   Events ev(st, kernel_ms4 != nullptr);
   HIPCHK(ev.create(5)); HIPCHK(ev.record(0));
   if (T) hipLaunchKernelGGL(sao_stats_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu, *T);
+  else if (SL) hipLaunchKernelGGL(sao_stats_slices, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu);
   else hipLaunchKernelGGL(sao_stats, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_stats, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(1));
@@ -692,6 +706,7 @@ static int sao_run(fcu_ctx *c, const char *name_, const LfTiles *T, int n_pics, 
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(3));
   if (T) hipLaunchKernelGGL(sao_apply_tiles, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu, *T);
+  else if (SL) hipLaunchKernelGGL(sao_apply_slices, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu);
   else hipLaunchKernelGGL(sao_apply, dim3(n_ctu, 3, n_pics), dim3(SAO_THREADS), 0, st, d_pics, d_recon, w, h, w_ctu, n_ctu);
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(4));
@@ -707,7 +722,7 @@ int fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint
                 int beta_offset_div2, int tc_offset_div2, float *kernel_ms2, void *hip_stream)
 {
   if (!c) return fail(FCU_ERR_ARG, "fcu_deblock: bad argument");
-  return deblock_run(c, "fcu_deblock", nullptr, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
+  return deblock_run(c, "fcu_deblock", nullptr, nullptr, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
 }
 
 int fcu_deblock_tiles(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
@@ -717,14 +732,14 @@ int fcu_deblock_tiles(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y
   LfTiles T;
   const int rc = lf_tiles_arg(c, n_cols, n_rows, lf_cross_tiles, "fcu_deblock_tiles", T);
   if (rc != FCU_OK) return rc;
-  return deblock_run(c, "fcu_deblock_tiles", &T, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
+  return deblock_run(c, "fcu_deblock_tiles", &T, nullptr, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
 }
 
 int fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t *const *dev_org, uint8_t *const *dev_rec,
             fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
 {
   if (!c) return fail(FCU_ERR_ARG, "fcu_sao: bad argument");
-  return sao_run(c, "fcu_sao", nullptr, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
+  return sao_run(c, "fcu_sao", nullptr, false, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
 }
 
 int fcu_sao_tiles(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int n_cols, int n_rows, int lf_cross_tiles,
@@ -734,7 +749,27 @@ int fcu_sao_tiles(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int n_co
   LfTiles T;
   const int rc = lf_tiles_arg(c, n_cols, n_rows, lf_cross_tiles, "fcu_sao_tiles", T);
   if (rc != FCU_OK) return rc;
-  return sao_run(c, "fcu_sao_tiles", &T, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
+  return sao_run(c, "fcu_sao_tiles", &T, false, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
+}
+
+int fcu_deblock_slices(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                       int beta_offset_div2, int tc_offset_div2, int slice_ctus, int lf_cross_slices, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_deblock_slices: bad argument");
+  const int rc = lf_slices_arg(slice_ctus, lf_cross_slices, "fcu_deblock_slices");
+  if (rc != FCU_OK) return rc;
+  LfSlices S;
+  const bool cut = lf_slices_fill(S, c->hs.n_ctu, slice_ctus, lf_cross_slices);      /* false: fcu_deblock's kernels */
+  return deblock_run(c, "fcu_deblock_slices", nullptr, cut ? &S : nullptr, dev_out, dev_rec_y, dev_rec_u, dev_rec_v, beta_offset_div2, tc_offset_div2, kernel_ms2, hip_stream);
+}
+
+int fcu_sao_slices(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int lf_cross_slices,
+                   const uint8_t *const *dev_org, uint8_t *const *dev_rec, fcu_sao_ctu *dev_coded, int32_t *off_count, float *kernel_ms4, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_sao_slices: bad argument");
+  const int rc = lf_slices_arg(0, lf_cross_slices, "fcu_sao_slices");       /* (each picture's slice_ctus: sao_run) */
+  if (rc != FCU_OK) return rc;
+  return sao_run(c, "fcu_sao_slices", nullptr, lf_cross_slices == 0, n_pics, params, dev_org, dev_rec, dev_coded, off_count, kernel_ms4, hip_stream);
 }
 
 void fcu_sao_enabled(const double rate[3][8], int layer, int32_t enabled[3])

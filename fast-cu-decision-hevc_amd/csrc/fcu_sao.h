@@ -17,13 +17,20 @@
  *                choice, and the reconstruction of merged parameters (see sao_decide_picture below).
  *   sao_apply    one workgroup per (CTU, component, picture): offsetBlock (:317-556) from the untouched copy of the
  *                deblocked picture into the reconstruction.  HBM-bound: reads src, writes rec.
- * 8-bit 4:2:0, 64x64 CTUs, LFCrossSliceBoundaryFlag 1.  Without tiles neighbour availability is the picture boundary
- * (TComPicSym.cpp:357-376) and merge candidates stay inside the CTU's slice (TComPic.cpp:138-143).
- * Tiles (fcu_sao_tiles) are a compile-time variant of the kernel bodies, TILES = true, which takes the grid (LfTiles, fcu_host.h)
+ * 8-bit 4:2:0, 64x64 CTUs.  Without tiles and with LFCrossSliceBoundaryFlag 1 neighbour availability is the picture boundary
+ * (TComPicSym.cpp:357-376); merge candidates stay inside the CTU's slice (TComPic.cpp:138-143) whatever that flag says.
+ * Slices with LFCrossSliceBoundaryFlag 0 (fcu_sao_slices) are the compile-time variant CUT = LF_CUT_SLICES of the statistics and of
+ * the offset pass; each picture's slice length is SaoPic::slice_ctus, so the kernels take no further argument.  A neighbour CTU
+ * is then available iff it is inside the picture and in the CTU's slice (TComPicSym.cpp:357-447), in eight directions of their
+ * own: once a slice starts or ends mid-row the diagonals are not the conjunction of their sides (sao_slice_avail).  The offset
+ * pass takes all eight (TComSampleAdaptiveOffset.cpp:577); the statistics take L, A and AL and keep R and B -- with them the
+ * skipped right / bottom margins -- at the picture border, as TEncSampleAdaptiveOffset.cpp:327-336 does ("For simplicity, here
+ * only picture boundaries are considered").  sao_cands and sao_decide serve as they are: the walk and the coder cross slices.
+ * Tiles (fcu_sao_tiles) are a compile-time variant of the kernel bodies, CUT = LF_CUT_TILES, which takes the grid (LfTiles, fcu_host.h)
  * by value: a merge candidate must lie in the CTU's tile (TComPic.cpp:138-143) whatever LFCrossTileBoundaryFlag says, and with
  * the flag 0 a CTU of another tile is unavailable to the statistics and the offset pass in all eight directions
  * (deriveLoopFilterBoundaryAvailibility, TComPicSym.cpp:378,449-459).  decideBlkParams still walks the picture in raster order and
- * carries the coder across tile boundaries.  TILES = false is the code as it was: the kernels fcu_sao launches do not change.
+ * carries the coder across tile boundaries.  CUT = LF_CUT_NONE is the code as it was: the kernels fcu_sao launches do not change.
  * Algorithmic bytes per picture: stats 2 x 1.5 W H read; apply 1.5 W H read + <= 1.5 W H written.
  */
 #pragma once
@@ -49,7 +56,21 @@ __device__ static inline void sao_tile_avail(const LfTiles &T, int cx, int cy, i
   L = L && !lf_tile_start(T.col, cx); R = R && !lf_tile_start(T.col, cx + 1);
   A = A && !lf_tile_start(T.row, cy); B = B && !lf_tile_start(T.row, cy + 1);
 }
-template <int PHASE, bool TILES = false>
+/* The eight availabilities of CTU a = cy * w_ctu + cx with LFCrossSliceBoundaryFlag 0 and S CTUs per slice: in come L / R / A / B
+ * of the picture border, out goes "inside the picture and in [first, last], the CTU's slice"
+ * (deriveLoopFilterBoundaryAvailibility, TComPicSym.cpp:357-447: HM picks the diagonal neighbours by the picture border, :373-389,
+ * and tests each one's own slice).  A slice that starts or ends mid-row separates a diagonal from its sides:
+ *   AR without A   a - w_ctu + 1 is the slice's first CTU        AL missing with A and L   a - w_ctu is its first CTU
+ *   BL without B   a + w_ctu - 1 is its last CTU                 BR missing with B and R   a + w_ctu is its last CTU
+ * Wave-uniform: a workgroup is one CTU. */
+__device__ static inline void sao_slice_avail(int S, int a, int w_ctu, int n_ctu, int &L, int &R, int &A, int &B, int &AL, int &AR, int &BL, int &BR)
+{
+  const int first = a - a % S, last = (first + S < n_ctu ? first + S : n_ctu) - 1;
+  AL = A && L && a - w_ctu - 1 >= first; AR = A && R && a - w_ctu + 1 >= first;
+  BL = B && L && a + w_ctu - 1 <= last;  BR = B && R && a + w_ctu + 1 <= last;
+  L = L && a - 1 >= first; R = R && a + 1 <= last; A = A && a - w_ctu >= first; B = B && a + w_ctu <= last;
+}
+template <int PHASE, int CUT = LF_CUT_NONE>
 __device__ static inline void sao_stats_phase(int32_t *hist, const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu, const LfTiles &T = LfTiles())
 {
   const int t = (int)threadIdx.x, a = (int)blockIdx.x, comp = (int)blockIdx.y, pic = (int)blockIdx.z;
@@ -59,8 +80,12 @@ __device__ static inline void sao_stats_phase(int32_t *hist, const SaoPic *pics,
   const int sh = comp ? 1 : 0, cx = a % w_ctu, cy = a / w_ctu, x0 = cx * 64, y0 = cy * 64;
   const int bw = (x0 + 64 > width ? width - x0 : 64) >> sh, bh = (y0 + 64 > height ? height - y0 : 64) >> sh, stride = width >> sh;
   int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height;
-  if (TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
-  const int AL = A && L;
+  if (CUT == LF_CUT_TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
+  int AL = A && L;
+  if (CUT == LF_CUT_SLICES) {                               /* L, A and AL by the slice; R and B stay the picture border's (TEncSampleAdaptiveOffset.cpp:332-336) */
+    int r_ = R, b_ = B, ar_, bl_, br_;
+    sao_slice_avail(P.slice_ctus > 0 ? P.slice_ctus : n_ctu, a, w_ctu, n_ctu, L, r_, A, b_, AL, ar_, bl_, br_);
+  }
   const int skipR = comp ? 3 : 5, skipB = comp ? 2 : 4;
   const int sx = L ? 0 : 1, ex = R ? bw - skipR : bw - 1, exFull = R ? bw - skipR : bw;
   const int eyFull = B ? bh - skipB : bh, ey = B ? bh - skipB : bh - 1;
@@ -297,9 +322,9 @@ struct SaoNb { int left, above; };                         /* merge candidates: 
  *                 coder chroma starts from depends on luma only through the sao_type_idx bin luma coded -- the counter is
  *                 reset to its Q15 remainder, which whole bypass bins do not change -- so there are two cases, not six;
  *   lanes 32..37  distortion of the left / above CTU's parameters on this CTU's statistics, per component (:760-766). */
-/* (TILES does nothing in sao_ctu_costs / sao_ctu_choose: it gives each kernel variant its own copy, so that sao_decide sees the
+/* (CUT does nothing in sao_ctu_costs / sao_ctu_choose: it gives each kernel variant its own copy, so that sao_decide sees the
  * call graph it had -- one caller per helper -- and comes out of the inliner as it did) */
-template <bool TILES>
+template <int CUT>
 __device__ static inline void sao_ctu_costs(int lane, SaoDecideLds &L, const int32_t *st, const SaoCand *cd, int a, int w_ctu, const SaoNb nb)
 {
   const int en0 = L.en[0], en1 = L.en[1], en2 = L.en[2];
@@ -349,7 +374,7 @@ __device__ static inline void sao_ctu_costs(int lane, SaoDecideLds &L, const int
   }
 }
 /* Second half, lane 0: the choices in the reference's order, the coder after the CTU, the CTU's reconstructed parameters */
-template <bool TILES>
+template <int CUT>
 __device__ static inline void sao_ctu_choose(SaoDecideLds &L, const SaoCand *cd, int a, int w_ctu, const SaoNb nb)
 {
   const int en0 = L.en[0], en1 = L.en[1], en2 = L.en[2];
@@ -412,7 +437,7 @@ __device__ static inline void sao_ctu_choose(SaoDecideLds &L, const SaoCand *cd,
 }
 /* coded[] = parameters as signalled, recon[] = after reconstructBlkSAOParam, off_count[comp] = CTUs whose reconstructed mode is
  * OFF (-> m_saoDisabledRate) */
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t *stats, const SaoCand *cands, fcu_sao_ctu *coded, fcu_sao_ctu *recon,
                                                  int32_t *off_count, int w_ctu, int n_ctu, SaoDecideLds &L, const LfTiles &T = LfTiles())
 {
@@ -435,11 +460,11 @@ __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t
     SAO_PHASE { if (a + 1 < n_ctu) sao_fetch(lane, stats, cands, a + 1, pre[SAO_L]); }
     if (slice_ctus > 0 && a == sliceStart + slice_ctus) sliceStart = a;
     SaoNb nb; nb.above = cy > 0 && a - w_ctu >= sliceStart; nb.left = cx > 0 && a - 1 >= sliceStart;
-    if (TILES) { nb.above = nb.above && !lf_tile_start(T.row, cy); nb.left = nb.left && !lf_tile_start(T.col, cx); }      /* the candidate's tile: either value of the flag */
+    if (CUT == LF_CUT_TILES) { nb.above = nb.above && !lf_tile_start(T.row, cy); nb.left = nb.left && !lf_tile_start(T.col, cx); }      /* the candidate's tile: either value of the flag */
     if (++cx == w_ctu) { cx = 0; cy++; }
-    SAO_PHASE { sao_ctu_costs<TILES>(lane, L, L.stats[a & 1], L.cand[a & 1], a, w_ctu, nb); }
+    SAO_PHASE { sao_ctu_costs<CUT>(lane, L, L.stats[a & 1], L.cand[a & 1], a, w_ctu, nb); }
     SAO_SYNC();
-    SAO_PHASE { if (lane == 0) sao_ctu_choose<TILES>(L, L.cand[a & 1], a, w_ctu, nb); }
+    SAO_PHASE { if (lane == 0) sao_ctu_choose<CUT>(L, L.cand[a & 1], a, w_ctu, nb); }
     SAO_PHASE { if (a + 1 < n_ctu) sao_stash(lane, pre[SAO_L], L.stats[(a + 1) & 1], L.cand[(a + 1) & 1]); }
     SAO_SYNC();
     SAO_PHASE {                                               /* the CTU's two records, a dword per lane */
@@ -457,7 +482,7 @@ __device__ static inline void sao_decide_picture(const SaoPic &P_, const int32_t
 }
 
 /* ---- offsetBlock, TComSampleAdaptiveOffset.cpp:317-556 -------------------------------------------------------------- */
-template <bool TILES = false>
+template <int CUT = LF_CUT_NONE>
 __device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu, const LfTiles &T = LfTiles())
 {
   const int t = (int)threadIdx.x, a = (int)blockIdx.x, comp = (int)blockIdx.y, pic = (int)blockIdx.z;
@@ -467,8 +492,9 @@ __device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_
   const int sh = comp ? 1 : 0, cx = a % w_ctu, cy = a / w_ctu, x0 = cx * 64, y0 = cy * 64;
   const int w = (x0 + 64 > width ? width - x0 : 64) >> sh, h = (y0 + 64 > height ? height - y0 : 64) >> sh, stride = width >> sh;
   int L = cx > 0, R = x0 + 64 < width, A = cy > 0, B = y0 + 64 < height;
-  if (TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
-  const int AL = A && L, AR = A && R, BL = B && L, BR = B && R;
+  if (CUT == LF_CUT_TILES) sao_tile_avail(T, cx, cy, L, R, A, B);
+  int AL = A && L, AR = A && R, BL = B && L, BR = B && R;
+  if (CUT == LF_CUT_SLICES) sao_slice_avail(P.slice_ctus > 0 ? P.slice_ctus : n_ctu, a, w_ctu, n_ctu, L, R, A, B, AL, AR, BL, BR);
   const int sx = L ? 0 : 1, ex = R ? w : w - 1, type = p.type;
   const size_t o0 = (size_t)(y0 >> sh) * stride + (x0 >> sh);
   const uint8_t *src = P.src[comp] + o0; uint8_t *res = P.rec[comp] + o0;
@@ -481,14 +507,14 @@ __device__ static inline void sao_apply_block(const SaoPic *pics, const fcu_sao_
     else if (type == 1) { if (y >= (A ? 0 : 1) && y < (B ? h : h - 1)) k = 2 + sao_sgn(c - s[-stride]) + sao_sgn(c - s[stride]); }
     else if (type == 2) {
       int ok;
-      if (y == 0) ok = A && x >= (AL ? 0 : 1) && x < ex;
+      if (y == 0) ok = CUT == LF_CUT_SLICES ? (x >= (AL ? 0 : 1) && x < (A ? ex : 1)) : (A && x >= (AL ? 0 : 1) && x < ex);      /* (:431-432 as written; the same while AL implies A) */
       else if (y == h - 1) ok = x >= (B ? sx : w - 1) && x < (BR ? w : w - 1);
       else ok = x >= sx && x < ex;
       if (ok) k = 2 + sao_sgn(c - s[-stride - 1]) + sao_sgn(c - s[stride + 1]);
     } else if (type == 3) {
       int ok;
       if (y == 0) ok = x >= (A ? sx : w - 1) && x < (AR ? w : w - 1);
-      else if (y == h - 1) ok = B && x >= (BL ? 0 : 1) && x < ex;
+      else if (y == h - 1) ok = CUT == LF_CUT_SLICES ? (x >= (BL ? 0 : 1) && x < (B ? ex : 1)) : (B && x >= (BL ? 0 : 1) && x < ex);      /* (:525-526 as written: BL without B filters x = 0) */
       else ok = x >= sx && x < ex;
       if (ok) k = 2 + sao_sgn(c - s[-stride + 1]) + sao_sgn(c - s[stride - 1]);
     } else k = c >> 3;
@@ -522,22 +548,34 @@ __global__ void __launch_bounds__(SAO_THREADS) sao_apply(const SaoPic *pics, con
 __global__ void __launch_bounds__(SAO_THREADS) sao_stats_tiles(const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu, LfTiles T)
 {
   __shared__ int32_t hist[SAO_STAT_INTS];
-  sao_stats_phase<0, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+  sao_stats_phase<0, LF_CUT_TILES>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
   __syncthreads();
-  sao_stats_phase<1, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+  sao_stats_phase<1, LF_CUT_TILES>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
   __syncthreads();
-  sao_stats_phase<2, true>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
+  sao_stats_phase<2, LF_CUT_TILES>(hist, pics, stats, width, height, w_ctu, n_ctu, T);
 }
 __global__ void __launch_bounds__(64) sao_decide_tiles(const SaoPic *pics, const int32_t *stats, const SaoCand *cands, fcu_sao_ctu *coded, fcu_sao_ctu *recon,
                                                        int32_t *off_count, int w_ctu, int n_ctu, int n_pics, LfTiles T)
 {
   __shared__ SaoDecideLds L;
   const int pic = (int)blockIdx.x;
-  sao_decide_picture<true>(pics[pic], stats + (size_t)pic * n_ctu * 3 * SAO_STAT_INTS, cands + (size_t)pic * n_ctu * 15,
+  sao_decide_picture<LF_CUT_TILES>(pics[pic], stats + (size_t)pic * n_ctu * 3 * SAO_STAT_INTS, cands + (size_t)pic * n_ctu * 15,
                            coded + (size_t)pic * n_ctu, recon + (size_t)pic * n_ctu, off_count + pic * 3, w_ctu, n_ctu, L, T);
 }
 __global__ void __launch_bounds__(SAO_THREADS) sao_apply_tiles(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu, LfTiles T)
-{ sao_apply_block<true>(pics, recon, width, height, w_ctu, n_ctu, T); }
+{ sao_apply_block<LF_CUT_TILES>(pics, recon, width, height, w_ctu, n_ctu, T); }
+/* the slice variants fcu_sao_slices launches with LFCrossSliceBoundaryFlag 0 (sao_cands and sao_decide serve as they are) */
+__global__ void __launch_bounds__(SAO_THREADS) sao_stats_slices(const SaoPic *pics, int32_t *stats, int width, int height, int w_ctu, int n_ctu)
+{
+  __shared__ int32_t hist[SAO_STAT_INTS];
+  sao_stats_phase<0, LF_CUT_SLICES>(hist, pics, stats, width, height, w_ctu, n_ctu);
+  __syncthreads();
+  sao_stats_phase<1, LF_CUT_SLICES>(hist, pics, stats, width, height, w_ctu, n_ctu);
+  __syncthreads();
+  sao_stats_phase<2, LF_CUT_SLICES>(hist, pics, stats, width, height, w_ctu, n_ctu);
+}
+__global__ void __launch_bounds__(SAO_THREADS) sao_apply_slices(const SaoPic *pics, const fcu_sao_ctu *recon, int width, int height, int w_ctu, int n_ctu)
+{ sao_apply_block<LF_CUT_SLICES>(pics, recon, width, height, w_ctu, n_ctu); }
 #endif
 
 } /* namespace fcu */

@@ -182,7 +182,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
-           "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match"]
+           "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -251,6 +251,8 @@ def load_lib():
     lib.fcu_sao.argtypes = [C.c_void_p, C.c_int, C.POINTER(SaoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_deblock_tiles.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5 + [C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_sao_tiles.argtypes = [C.c_void_p, C.c_int, C.POINTER(SaoParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_deblock_slices.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_sao_slices.argtypes = [C.c_void_p, C.c_int, C.POINTER(SaoParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_sao_enabled.restype = None
     lib.fcu_sao_enabled.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.fcu_sao_update_rate.restype = None
@@ -652,14 +654,19 @@ class CuEngine:
         return trace.cpu().numpy().view(PU_TRACE_DTYPE).reshape(self.n_ctu, PUS_PER_CTU)
 
     # -- TComLoopFilter::loopFilterPic
-    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1, layout=None):
+    def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1, slice_ctus=None, lf_cross_slices=1, layout=None):
         """Deblocks, in place, the reconstruction planes bound to `chain` (all slice chains of a picture share them)
         once every CTU of the picture has been decided -- or explicit device tensors: `out` = the picture's
         fcu_ctu_out array as uint8, `rec` = (Y, U, V).  tiles=(C, R): the picture's uniform tile grid, filtered with
         LFCrossTileBoundaryFlag = lf_cross_tiles (fcu_deblock_tiles; 0 leaves the tile boundaries unfiltered); without tiles
-        lf_cross_tiles is not looked at; layout: a PictureLayout to take both from.  Returns (ms vertical pass, ms horizontal pass) if timed."""
+        lf_cross_tiles is not looked at.  slice_ctus: CTUs per slice of a picture of SliceMode 1 slices, filtered with
+        LFCrossSliceBoundaryFlag = lf_cross_slices (fcu_deblock_slices; 0 leaves the slice boundaries unfiltered); None: fcu_deblock,
+        the flag 1.  layout: a PictureLayout to take all four from.  Returns (ms vertical pass, ms horizontal pass) if timed."""
         if layout is not None:
             tiles, lf_cross_tiles = layout.tiles, layout.lf_cross_tiles
+            slice_ctus, lf_cross_slices = (layout.sao_slice_ctus, layout.lf_cross_slices) if layout.lf_cross_slices != 1 else (None, 1)
+        if tiles is not None and slice_ctus:
+            raise ValueError("CuEngine.deblock: tiles need one slice per picture (no slice_ctus)")
         if chain is not None:
             _, rec, out = self._keep[chain]
         assert out.numel() >= self.n_ctu * CTU_OUT_BYTES and rec[0].numel() == self.width * self.height
@@ -668,22 +675,27 @@ class CuEngine:
         if tiles is not None:
             self._chk(self.lib.fcu_deblock_tiles(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
                                                  beta_offset_div2, tc_offset_div2, int(tiles[0]), int(tiles[1]), int(lf_cross_tiles), ms, s), "fcu_deblock_tiles")
+        elif slice_ctus is not None:
+            self._chk(self.lib.fcu_deblock_slices(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
+                                                  beta_offset_div2, tc_offset_div2, int(slice_ctus), int(lf_cross_slices), ms, s), "fcu_deblock_slices")
         else:
             self._chk(self.lib.fcu_deblock(self.h, out.data_ptr(), rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
                                            beta_offset_div2, tc_offset_div2, ms, s), "fcu_deblock")
         return (ms[0], ms[1]) if timed else None
 
     # -- TEncSampleAdaptiveOffset::SAOProcess
-    def sao(self, pictures, timed=False, stream=None, tiles=None, lf_cross_tiles=1, layout=None):
+    def sao(self, pictures, timed=False, stream=None, tiles=None, lf_cross_tiles=1, lf_cross_slices=1, layout=None):
         """SAO of completely decided, deblocked pictures, in place on their reconstruction planes.  pictures: list of dicts
         {org: (Y,U,V) device tensors, rec: (Y,U,V) device tensors, qp, lambda_ (the slice's luma lambda), slice_type,
         slice_ctus, enabled (3 ints, default all on), chroma_weight (default: from the QP, chroma QP offset 0)}.
         tiles=(C, R): every picture of the batch is cut into C x R uniform tiles (fcu_sao_tiles): merge candidates stay inside
         the CTU's tile, and with lf_cross_tiles=0 (LFCrossTileBoundaryFlag) so do the samples the statistics and the offset pass
-        read; slice_ctus must then be 0; layout: a PictureLayout to take both from.  Returns (coded uint8 tensor
+        read; slice_ctus must then be 0.  lf_cross_slices: LFCrossSliceBoundaryFlag of the pictures' slices (each picture's
+        slice_ctus); 0 (fcu_sao_slices) keeps the samples the statistics and the offset pass read inside the CTU's slice.
+        layout: a PictureLayout to take all three from.  Returns (coded uint8 tensor
         [n, n_ctu, SAO_CTU_BYTES] on the device, off_count int32 array [n, 3], kernel ms x4 or None)."""
         if layout is not None:
-            tiles, lf_cross_tiles = layout.tiles, layout.lf_cross_tiles
+            tiles, lf_cross_tiles, lf_cross_slices = layout.tiles, layout.lf_cross_tiles, layout.lf_cross_slices
         torch = self.torch
         n = len(pictures)
         dev = torch.device("cuda", self.device)
@@ -705,6 +717,8 @@ class CuEngine:
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         if tiles is not None:
             self._chk(self.lib.fcu_sao_tiles(self.h, n, prm, int(tiles[0]), int(tiles[1]), int(lf_cross_tiles), org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao_tiles")
+        elif lf_cross_slices != 1:
+            self._chk(self.lib.fcu_sao_slices(self.h, n, prm, int(lf_cross_slices), org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao_slices")
         else:
             self._chk(self.lib.fcu_sao(self.h, n, prm, org, rec, coded.data_ptr(), off.ctypes.data, ms, s), "fcu_sao")
         return coded, off, (list(ms) if timed else None)

@@ -9,9 +9,10 @@ class PictureLayout:
     wpp: WaveFrontSynchro -- the CTU rows are chains; slice_rows (with wpp only): slices of slice_rows whole CTU rows.
     tiles=(C, R): one slice cut into C x R uniform tiles, with wpp WaveFrontSynchro inside every tile; lf_cross_tiles (with
     tiles only): LFCrossTileBoundaryFlag of the loop filters, None = 1; sao / tmvp: what the caller runs on such a picture
-    (SAO with tiles needs the flag chosen; TMVP cannot cross tile columns).  who: prefix of the ValueError messages."""
+    (SAO with tiles needs the flag chosen; TMVP cannot cross tile columns).  lf_cross_slices (with slices only: a non-zero
+    slice_ctus, or slice_rows): LFCrossSliceBoundaryFlag of the loop filters, None = 1.  who: prefix of the ValueError messages."""
 
-    def __init__(self, width, height, slice_ctus=None, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, sao=False, tmvp=False, who=""):
+    def __init__(self, width, height, slice_ctus=None, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, sao=False, tmvp=False, who="", *, lf_cross_slices=None):
         def refuse(msg):
             raise ValueError(f"{who}: {msg}" if who else msg)
         self.w_ctu, self.h_ctu = (width + 63) // 64, (height + 63) // 64
@@ -29,6 +30,13 @@ class PictureLayout:
                 refuse("tmvp together with tile columns is not supported (the collocated bottom-right candidate reads across the tile edge)")
         elif lf_cross_tiles is not None:
             refuse("lf_cross_tiles is the loop filters' flag of a picture with tiles and needs tiles=(C, R)")
+        if lf_cross_slices is not None:
+            if tiles is not None:
+                refuse("lf_cross_slices is the loop filters' flag of a picture with slices; tiles need one slice per picture (the tiles' flag: lf_cross_tiles)")
+            if lf_cross_slices not in (0, 1):
+                refuse("lf_cross_slices (LFCrossSliceBoundaryFlag) is 0 or 1")
+            if not slice_ctus and slice_rows is None:
+                refuse("lf_cross_slices is the loop filters' flag of a picture with slices and needs slice_ctus, or wpp=True with slice_rows")
         if wpp and slice_ctus:
             refuse("wpp needs one slice per picture (slice_ctus must be None; slices of whole CTU rows: slice_rows)")
         if slice_rows is not None and not wpp:
@@ -37,6 +45,7 @@ class PictureLayout:
             refuse("slice_rows must be at least 1")
         self.wpp, self.slice_rows, self.tiles = bool(wpp), slice_rows, tiles
         self.lf_cross_tiles = 1 if lf_cross_tiles is None else lf_cross_tiles
+        self.lf_cross_slices = 1 if lf_cross_slices is None else lf_cross_slices
         self.slice_ctus = slice_ctus if slice_ctus else self.n_ctu
         self.n_slices = (self.n_ctu + self.slice_ctus - 1) // self.slice_ctus      # SliceMode 1 slices (1 with wpp and with tiles)
         sliced = self.n_slices > 1
@@ -45,7 +54,7 @@ class PictureLayout:
         else:
             self.chains = self.h_ctu if wpp else self.n_slices                     # chains per picture: rows (WPP) or slices
         self.bind_slice_ctus = self.slice_ctus if sliced else 0                    # fcu_frame_params.slice_ctus of fcu_chain_begin
-        self.sao_slice_ctus = slice_rows * self.w_ctu if slice_rows is not None else self.bind_slice_ctus      # what fcu_sao is told
+        self.sao_slice_ctus = slice_rows * self.w_ctu if slice_rows is not None else self.bind_slice_ctus      # what fcu_sao and fcu_deblock_slices are told
         self.launch_ctus = self.slice_ctus if sliced else self.n_ctu               # `ctus` of compress_chains: every chain to its end
         self.uses_wpp_launch = self.wpp                                            # compress_wpp instead of compress_chains
 

@@ -7,7 +7,8 @@ the parallelism of a launch comes from the slices of a picture and from independ
 is chain s * n_slices + k.  Per picture: fcu_ldp_slice (QP / lambda of HM's lowdelay_P GOP table) -> fcu_chain_begin
 (+ fcu_chain_set_reference for P) -> one fcu_compress_chains launch over all chains -> fcu_deblock -> fcu_sao (SAO 1, the
 reference's lowdelay configuration; one batched call for all clips) -> fcu_pad_reference.  A picture with tiles goes through
-fcu_deblock_tiles / fcu_sao_tiles instead, with the LFCrossTileBoundaryFlag the caller chose.
+fcu_deblock_tiles / fcu_sao_tiles instead, with the LFCrossTileBoundaryFlag the caller chose; a picture with slices and
+lf_cross_slices=0 through fcu_deblock_slices / fcu_sao_slices, so that the next picture references the LFCrossSliceBoundaryFlag 0 result.
 Across GPUs the reference picture is the only data a rank would need from another one (one copy per picture, SURVEY.md 8e);
 with whole clips per rank there is none.
 
@@ -59,7 +60,7 @@ class LowDelayPDecider:
     wpp: WaveFrontSynchro=1 -- one slice per picture whose CTU rows run as chains (module docstring)."""
 
     def __init__(self, width, height, base_qp, n_clips=1, search_range=64, slice_ctus=None, deblock=True, sao=False, tmvp=False, fast_search=1, amp=False, device=0,
-                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None):
+                 n_refs=1, rps="hm", wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None):
         """n_refs: reference pictures in list 0 (the reference cfg's num_ref_idx_active is 4; 1 = the previous picture only);
         rps: which pictures those are (ref_pocs above).
         tiles=(C, R): every picture is one slice cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
@@ -68,6 +69,9 @@ class LowDelayPDecider:
         lf_cross_tiles (with tiles only): LFCrossTileBoundaryFlag of the loop filters, 0 or 1 -- whether deblocking filters the
         tile boundaries and SAO reads samples across them (fcu_deblock_tiles / fcu_sao_tiles).  None means 1 for deblocking,
         HM's default; sao=True together with tiles asks for an explicit choice.
+        lf_cross_slices (with slice_ctus, or wpp=True and slice_rows, only): LFCrossSliceBoundaryFlag of the loop filters, 0 or 1 --
+        whether deblocking filters the slice boundaries and SAO reads samples across them (fcu_deblock_slices / fcu_sao_slices).
+        None means 1, HM's default.
         report=True: every result dict gains `report`, the picture report (CuEngine.report: SSD / PSNR per plane, bits, CU
         statistics) of the final planes, taken on the device in one batched call for all clips.
         pic_hash="md5", "crc" or "checksum": every result dict gains `hash`, HM's decoded-picture hash string of the final planes
@@ -80,8 +84,9 @@ class LowDelayPDecider:
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("LowDelayPDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
         self.pic_hash = pic_hash
-        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, tmvp=tmvp, who="LowDelayPDecider")
+        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, tmvp=tmvp, who="LowDelayPDecider", lf_cross_slices=lf_cross_slices)
         self.tiles, self.lf_cross_tiles, self.wpp, self.slice_rows, self.slice_ctus = tiles, lo.lf_cross_tiles, wpp, slice_rows, lo.slice_ctus
+        self.lf_cross_slices = lo.lf_cross_slices
         self.n_slices, self.n_chains, self.sao_slice_ctus = lo.n_slices, lo.chains, lo.sao_slice_ctus
         self.width, self.height, self.base_qp, self.n_clips, self.search_range = width, height, base_qp, n_clips, search_range
         self.carry_search_state = lo.wpp and slice_rows is None and tiles is None      # one slice of WPP rows: HM's state goes from picture to picture

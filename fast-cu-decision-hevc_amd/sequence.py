@@ -96,7 +96,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, **flags):
         """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
@@ -105,7 +105,9 @@ class SequenceDecider:
         (fcu_wpp_begin / fcu_compress_wpp); the pictures in flight go in one launch.
         slice_rows (with wpp only): WaveFrontSynchro together with SliceMode 1, SliceArgument = slice_rows x the picture width in
         CTUs -- independent slices of slice_rows whole CTU rows whose rows run as chains (fcu_wpp_begin_slices): the first row of
-        a slice waits for nothing.  Deblocking crosses the slice boundaries as before (LFCrossSliceBoundaryFlag 1).
+        a slice waits for nothing.
+        lf_cross_slices (with slice_ctus or slice_rows only): LFCrossSliceBoundaryFlag of the deblocking, 0 or 1; None means 1,
+        HM's default -- deblocking crosses the slice boundaries; 0 leaves them unfiltered (fcu_deblock_slices).
         tiles=(C, R): one slice per picture cut into C x R uniform tiles (HM's TileUniformSpacing) decided as chains
         (fcu_tiles_begin), with wpp=True WaveFrontSynchro inside every tile (fcu_wpp_begin_tiles).  lf_cross_tiles (with tiles
         only): LFCrossTileBoundaryFlag of the deblocking, 0 or 1 (fcu_deblock_tiles); None means 1, HM's default -- deblocking
@@ -125,10 +127,11 @@ class SequenceDecider:
             raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
         self.pic_hash = pic_hash
         sao = flags.get("sao")
-        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, who="SequenceDecider")
+        self.layout = lo = PictureLayout(width, height, slice_ctus, wpp, slice_rows, tiles, lf_cross_tiles, sao=sao, who="SequenceDecider", lf_cross_slices=lf_cross_slices)
         if sao and tiles is not None:
             raise ValueError("SequenceDecider: sao=True is not supported: this driver runs no SAO (LowDelayPDecider(tiles=..., sao=True, lf_cross_tiles=...) does)")
         self.tiles, self.lf_cross_tiles, self.wpp, self.slice_rows, self.slice_ctus = tiles, lo.lf_cross_tiles, wpp, slice_rows, lo.slice_ctus
+        self.lf_cross_slices = lo.lf_cross_slices
         self.slice_mode, self.n_slices = lo.describe(), lo.chains      # n_slices: chains per picture (slices, rows or tile chains)
         self.width, self.height, self.qp, self.fast, self.do_deblock, self.flags = width, height, qp, fast, deblock, flags
         self.in_flight = max(1, in_flight)

@@ -23,12 +23,14 @@
  *   TEncSearch::estIntraPredLumaQT per-PU results  fcu_chain_set_pu_trace (BASELINE configs[1]: luma RDO artefact)
  *     (TEncSearch.cpp:2178-2655)
  *   TComLoopFilter::loopFilterPic                  fcu_deblock (in-loop deblocking of the decided picture);
- *     (TComLoopFilter.cpp:130, TEncGOP.cpp:1160)     a picture with tiles: fcu_deblock_tiles (LFCrossTileBoundaryFlag 0 or 1)
+ *     (TComLoopFilter.cpp:130, TEncGOP.cpp:1160)     a picture with tiles: fcu_deblock_tiles (LFCrossTileBoundaryFlag 0 or 1);
+ *                                                    slices: fcu_deblock_slices (LFCrossSliceBoundaryFlag 0 or 1, :369-411)
  *   TEncSampleAdaptiveOffset::SAOProcess           fcu_sao (statistics, per-CTU parameter decision, offset pass) +
  *     (TEncSampleAdaptiveOffset.cpp:257,              fcu_sao_enabled / fcu_sao_update_rate (decidePicParams and the
  *      TEncGOP.cpp:1427-1441)                         m_saoDisabledRate bookkeeping across pictures, :363-395,895-917);
  *                                                    a picture with tiles: fcu_sao_tiles (merge candidates inside the tile,
- *                                                    TComPic.cpp:138-143; LFCrossTileBoundaryFlag 0 or 1, TComPicSym.cpp:378,449-459)
+ *                                                    TComPic.cpp:138-143; LFCrossTileBoundaryFlag 0 or 1, TComPicSym.cpp:378,449-459);
+ *                                                    slices: fcu_sao_slices (LFCrossSliceBoundaryFlag 0 or 1, TComPicSym.cpp:357-447)
  *   WaveFrontSynchro=1 row loop of                 fcu_wpp_begin / fcu_wpp_begin_p (one chain per CTU row of a
  *     TEncSlice::compressSlice                       one-slice I / P picture), fcu_compress_wpp (every row of whole
  *     (TEncSlice.cpp:1386-1411,1514-1517)            pictures in one launch, a row waiting for the row above), fcu_wpp_rows
@@ -332,7 +334,8 @@ int  fcu_frame_state(int poc, int period, int n_training, int n_verifying);
 /* In-loop deblocking of a completely decided I or P picture, in place on its reconstruction planes:
  * TComLoopFilter::loopFilterPic (TComLoopFilter.cpp:130-155) as TEncGOP::compressGOP runs it after the last slice of the
  * picture (TEncGOP.cpp:1155-1160), with the encoder's default control -- filter enabled, LFCrossSliceBoundaryFlag 1
- * (TAppEncCfg.cpp:813-818,848-849) -- and the slice's beta / tc offsets (div 2, -6..6).  It knows no tiles: for a tile picture
+ * (TAppEncCfg.cpp:813-818,848-849; either value of that flag: fcu_deblock_slices) -- and the slice's beta / tc offsets (div 2,
+ * -6..6).  It knows no tiles: for a tile picture
  * it is the filter of LFCrossTileBoundaryFlag 1 (HM's default); either value of that flag: fcu_deblock_tiles.
  * dev_out is the picture's fcu_ctu_out array (depth, part_size, tr_idx and qp are read).  Two kernels on `hip_stream`;
  * asynchronous unless kernel_ms2 is given, which then receives the durations of the vertical- and horizontal-edge pass. */
@@ -346,6 +349,17 @@ int  fcu_deblock(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uin
 int  fcu_deblock_tiles(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
                        int beta_offset_div2, int tc_offset_div2, int n_cols, int n_rows, int lf_cross_tiles,
                        float *kernel_ms2, void *hip_stream);
+/* fcu_deblock of a picture of SliceMode 1 slices -- slice_ctus consecutive CTUs in raster order each, the last one what is
+ * left; a slice may start mid-row; 0, or the picture's CTU count and more, is one slice -- with LFCrossSliceBoundaryFlag =
+ * lf_cross_slices for all of them (TEncGOP.cpp:763).  1 filters a slice boundary like any other CTU boundary (what fcu_deblock
+ * does); with 0 a partition on the left / top edge of its CTU gets no edge flag when the CTU to the left / above lies in another
+ * slice, luma and chroma, as on the picture border (TComLoopFilter.cpp:369-411,430-434,609-613,754-758; TComDataCU::getPULeft /
+ * getPUAbove) -- the slices can then be filtered independently.  lf_cross_slices 1, or one slice, is fcu_deblock byte for byte
+ * (and runs its kernels).  The slice length is the whole description: no limit on the picture beyond fcu_deblock's.
+ * FCU_ERR_ARG: lf_cross_slices outside {0, 1}, a negative slice_ctus, and what fcu_deblock refuses. */
+int  fcu_deblock_slices(fcu_ctx *c, const fcu_ctu_out *dev_out, uint8_t *dev_rec_y, uint8_t *dev_rec_u, uint8_t *dev_rec_v,
+                        int beta_offset_div2, int tc_offset_div2, int slice_ctus, int lf_cross_slices,
+                        float *kernel_ms2, void *hip_stream);
 /* ---- sample adaptive offset --------------------------------------------------------------------------------------
  * SAOOffset / SAOBlkParam of the reference (TypeDef.h:760-800) narrowed to bytes: mode 0 off / 1 new / 2 merge;
  * type: edge class 0..3 or 4 = band offset for a new mode, 0 = left / 1 = above for a merge; band = band position;
@@ -355,7 +369,7 @@ typedef struct { fcu_sao_offset c[3]; } fcu_sao_ctu;                    /* Y, Cb
 typedef struct {
   int32_t slice_type;        /* FCU_SLICE_I / FCU_SLICE_P: context initialisation of the SAO syntax */
   int32_t qp;                /* slice QP */
-  int32_t slice_ctus;        /* SliceArgument (0 = one slice): merge candidates do not cross slices */
+  int32_t slice_ctus;        /* SliceArgument (0 = one slice): merge candidates do not cross slices; fcu_sao_slices: nor do samples */
   int32_t enabled[3];        /* slice-level switches (fcu_sao_enabled) */
   double  lambda[3];         /* TComSlice::getLambdas(): lambda, lambda / chroma weight (x2); [1], [2] = 0: derived from [0] and the QP (chroma QP offsets 0) */
 } fcu_sao_params;
@@ -380,6 +394,18 @@ int  fcu_sao(fcu_ctx *c, int n_pics, const fcu_sao_params *params, const uint8_t
 int  fcu_sao_tiles(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int n_cols, int n_rows, int lf_cross_tiles,
                    const uint8_t *const *dev_org, uint8_t *const *dev_rec, fcu_sao_ctu *dev_coded, int32_t *off_count,
                    float *kernel_ms4, void *hip_stream);
+/* fcu_sao with LFCrossSliceBoundaryFlag = lf_cross_slices; each picture's slices are its params[i].slice_ctus (as for
+ * fcu_deblock_slices; pictures of one batch may differ).  The decision is fcu_sao's for either value: merge candidates stay
+ * inside the slice, the walk and the coder cross slices.  With lf_cross_slices 0 a neighbour CTU is available to the offset pass
+ * iff it is inside the picture and in the CTU's slice, each of the eight directions on its own -- once a slice starts or ends
+ * mid-row a diagonal is not the conjunction of its sides (TComPicSym::deriveLoopFilterBoundaryAvailibility, TComPicSym.cpp:
+ * 357-447) --, and the statistics take left, above and above-left that way and keep right and below, with the margins they skip,
+ * at the picture border (TEncSampleAdaptiveOffset.cpp:327-336).  lf_cross_slices 1, or one slice in every picture, is fcu_sao
+ * byte for byte (and runs its kernels).  FCU_ERR_ARG: lf_cross_slices outside {0, 1} and what fcu_sao refuses (a negative
+ * slice_ctus among it). */
+int  fcu_sao_slices(fcu_ctx *c, int n_pics, const fcu_sao_params *params, int lf_cross_slices,
+                    const uint8_t *const *dev_org, uint8_t *const *dev_rec, fcu_sao_ctu *dev_coded, int32_t *off_count,
+                    float *kernel_ms4, void *hip_stream);
 /* decidePicParams (:363-395): enabled[comp] = 0 when the picture's temporal layer is > 0 and the share of SAO-off CTUs in
  * layer - 1 exceeded 0.75 (luma) / 0.5 (chroma).  rate = m_saoDisabledRate[3][8], zero-initialised by the caller per sequence. */
 void fcu_sao_enabled(const double rate[3][8], int layer, int32_t enabled[3]);

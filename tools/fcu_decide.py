@@ -16,7 +16,8 @@ the CTU rows of a picture are decided concurrently, each row starting from the c
 and waiting for the row above to stay two CTUs ahead.  --tiles CxR keeps one slice per picture and cuts it into C x R uniform
 tiles (HM's NumTileColumnsMinus1 / NumTileRowsMinus1 with TileUniformSpacing) decided concurrently; with --wpp the CTU rows of
 every tile are decided concurrently as well; --lf-cross-tiles 0 makes the deblocking leave the tile boundaries unfiltered (HM's
-LFCrossTileBoundaryFlag, default 1).  The slice mode is echoed on every picture line.
+LFCrossTileBoundaryFlag, default 1); --lf-cross-slices 0 does the same for the slice boundaries of --slice-ctus / --row-slices /
+--slice-rows (HM's LFCrossSliceBoundaryFlag, default 1).  The slice mode is echoed on every picture line.
 --report takes the picture line's figures from the device (fcu_picture_report): the PSNR, the picture's bits and the shares of
 intra / skipped / merged area; the reconstruction is then copied to the host only when --rec asks for the file.
 --hash md5|crc|checksum appends the decoded-picture hash of the reconstruction to the picture line exactly as the reference encoder
@@ -59,6 +60,7 @@ def main():
     ap.add_argument("--slice-rows", type=int, default=None, help="with --wpp: SliceMode 1 with slices of this many whole CTU rows, the rows of every slice decided as chains")
     ap.add_argument("--tiles", default=None, metavar="CxR", help="one slice per picture cut into C x R uniform tiles decided as chains; with --wpp, WaveFrontSynchro inside every tile")
     ap.add_argument("--lf-cross-tiles", type=int, choices=(0, 1), default=None, help="with --tiles: LFCrossTileBoundaryFlag of the deblocking (default 1: the tile boundaries are filtered)")
+    ap.add_argument("--lf-cross-slices", type=int, choices=(0, 1), default=None, help="with slices: LFCrossSliceBoundaryFlag of the deblocking (default 1: the slice boundaries are filtered)")
     ap.add_argument("--report", action="store_true", help="PSNR, bits and intra / skip / merge shares per picture from the device report; no plane is copied to the host unless --rec is given")
     ap.add_argument("--hash", choices=("md5", "crc", "checksum"), default=None, help="append HM's decoded-picture hash of the reconstruction to the picture line, taken on the device")
     ap.add_argument("--rec")
@@ -77,7 +79,7 @@ def main():
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
-        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, report=args.report, pic_hash=args.hash, maps=True if args.maps else None,
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None,
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
