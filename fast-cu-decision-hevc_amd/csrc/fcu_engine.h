@@ -304,6 +304,14 @@ struct Chain {
    * picture address are then the same number and nothing is masked.  The fields sit in the tail fcu_chain_set_decision copies
    * from the host descriptor, which therefore holds them too (ADVICE.md finding 4). */
   int tile_x0, tile_y0, tile_w, tile_h;
+  /* Caller-supplied split labels (fcu_chain_set_labels), written by the host only: labels = the PICTURE's label array, int8 [NL]
+   * in the layout fcu_decision_maps writes (level d = 0..3 one after the other, [ceil(height / s)][ceil(width / s)], s = 64 >> d),
+   * or null: the Naive model on N_OBF decides.  lbl_off[d] / lbl_w[d] = element offset and row length of level d.  A CU reads
+   * the label at its picture coordinates, so the slice, row and tile chains of a picture share one array.  The fields sit at the
+   * end of the tail fcu_chain_set_decision copies from the host descriptor, which holds them too; fcu_chain_set_labels copies
+   * them alone (CR_LABELS, fcu_host.h). */
+  const int8_t *labels;
+  int lbl_off[4], lbl_w[4];
 #ifdef FCU_EMU
   /* emulator only (the GPU layout has neither): bit r of wpp_mv_known = int_mv_r[r] holds HM's value (written by this row's
    * search, or taken from the caller / the row above); wpp_mv_rbw counts TZ searches that read a slot before it was known */
@@ -3472,6 +3480,15 @@ FCU_DEV FCU_NOINLINE int cu_num_obf(int x, int y, int s)
   }
   return FCU_UNI(g_S.dec_cnt);
 }
+/* The label a caller bound for the CU of depth D at picture position (x, y) (Chain::labels): one wave-uniform read.
+ * 1 = Skip2Nx2N ("will be divided"), 0 = TerminateCU, -1 = no prediction (any other code: FCU_LABEL_ABSENT, FCU_LABEL_FORCED ...) */
+template <int D>
+FCU_DEV int cu_label(const Chain *C, int x, int y)
+{
+  x = FCU_UNI(x); y = FCU_UNI(y);
+  const int v = ((const FCU_HBM int8_t *)C->labels)[C->lbl_off[D] + (y >> (6 - D)) * C->lbl_w[D] + (x >> (6 - D))];
+  return FCU_UNI(v == FCU_LABEL_SPLIT ? 1 : (v == FCU_LABEL_NOT_SPLIT ? 0 : -1));
+}
 /* countTFPN + countRDLoss (tools_YS.cpp:968-986; ResultType order TP,FP,TN,FN,FPLoss,FNLoss, globals_YS.h:81-89) */
 FCU_DEV void count_verify(Chain *C, int d, int predictSkip, int partitionTrue, double j0, double j1)
 {
@@ -3499,14 +3516,15 @@ FCU_DEV FCU_NOINLINE void compress_cu()
   const int x = b0->x, y = b0->y, zidx = b0->zidx, s = CTU >> D;
   const int boundary = !((x + s - 1 < P.width) && (y + s - 1 < P.height));
   const int state = E.C->dec_state;
-  int skip2Nx2N = 0, earlyTerminate = 0, predictSkip = 0;
+  /* predictSkip: 1 = the label Skip2Nx2N, 0 = TerminateCU, -1 = no prediction (a caller's label array may leave a CU open: it is
+   * searched exhaustively and not counted).  The Naive model always predicts. */
+  int skip2Nx2N = 0, earlyTerminate = 0, predictSkip = -1;
   if (!boundary && state != DEC_TRAINING) {
-    const int nobf = cu_num_obf(x, y, s);
-    predictSkip = nobf > 0;
-    if (state == DEC_TESTING) {                              /* TEncCu.cpp:951-996 */
+    predictSkip = E.C->labels ? cu_label<D>(E.C, x, y) : (cu_num_obf(x, y, s) > 0);
+    if (state == DEC_TESTING && predictSkip >= 0) {          /* TEncCu.cpp:951-996 */
       if (E.C->sw_term[D]) earlyTerminate = !predictSkip;
       if (E.C->sw_skip[D]) skip2Nx2N = predictSkip;
-      if (D == 3 && nobf > 0 && E.C->depth_exception) skip2Nx2N = earlyTerminate = 0;
+      if (D == 3 && predictSkip && E.C->depth_exception) skip2Nx2N = earlyTerminate = 0;
     }
   }
   if (!boundary) {
@@ -3558,6 +3576,8 @@ FCU_DEV FCU_NOINLINE void compress_cu()
       check_rd_cost_intra(D, SIZE_NxN);
       FCU_SERIAL { g_S.dec_flip ^= g_S.best_idx[D]; g_S.dec_j1 = g_S.dec_flip ? cu_best(E, D)->cost : cu_temp(E, D)->cost; }   /* :1175-1183 */
       cu_init(cu_temp(E, D), D, x, y, zidx);
+    } else if (D == MAXDEPTH && state == DEC_VERIFYING) {    /* NxN not tried (a P CU whose best inter candidate has no residual): */
+      FCU_SERIAL { g_S.dec_j0 = cu_best(E, D)->cost; g_S.dec_j1 = 0; g_S.dec_flip = 0; }      /* J1 0, bPartition_True false, not what the CU before left */
     }
     FCU_SERIAL {
       CuObj *best = cu_best(E, D);
@@ -3607,7 +3627,7 @@ FCU_DEV FCU_NOINLINE void compress_cu()
     FCU_SERIAL g_S.dec_flip ^= g_S.best_idx[D];              /* bPartition_True = xCheckBestMode(...) */
    }
   }
-  if (!boundary && state == DEC_VERIFYING) {                 /* TEncCu.cpp:1489-1497 */
+  if (!boundary && state == DEC_VERIFYING && predictSkip >= 0) {      /* TEncCu.cpp:1489-1497 */
     FCU_SERIAL count_verify(E.C, D, predictSkip, g_S.dec_flip, g_S.dec_j0, g_S.dec_j1);
   }
   cu_copy_to_pic(cu_best(E, D));

@@ -373,6 +373,21 @@ inline MapsGeom maps_geom(int width, int height, int n_fields, const int *field_
   for (int k = 0; k < n_fields; k++) G.field_off[k] = (uint16_t)maps_field_offset(field_ids[k]);
   return G;
 }
+/* fcu_chain_set_labels: the picture's label array (null: none) and the offsets and row lengths of its four levels -- the geometry
+ * of the label maps of fcu_decision_maps, from the one function that knows it */
+inline void chain_set_labels(Chain &h, const int8_t *labels)
+{
+  const MapsGeom G = maps_geom(h.p.width, h.p.height, 0, nullptr);
+  h.labels = labels;
+  for (int d = 0; d < 4; d++) { h.lbl_off[d] = G.lvl_off[d]; h.lbl_w[d] = G.lvl_w[d]; }
+}
+/* fcu_labels_from_rasters: what it refuses */
+inline int labels_args_check(int n_pics, const void *dev_depth, const void *dev_labels, std::string &err)
+{
+  const char *bad = n_pics < 1 ? "n_pics must be at least 1" : (!dev_depth ? "dev_depth is null" : (!dev_labels ? "dev_labels is null" : nullptr));
+  if (bad) { err = std::string("fcu_labels_from_rasters: ") + bad; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
 /* the unit the rows of the byte maps (and of the motion map) go out in: 16 bytes when every row of every map starts on 16 bytes
  * -- W4 a multiple of 16 (whole CTU columns, every map a multiple of 16 bytes) and aligned bases --, else 2-byte units, which
  * W4 even always allows; their alignment is the base's: 2, or 1 for a byte map at an odd address */
@@ -436,6 +451,10 @@ constexpr ChainRange CR_RANGE = { offsetof(Chain, next_ctu), 2 * sizeof(int) }; 
 static_assert(offsetof(Chain, end_ctu) == offsetof(Chain, next_ctu) + sizeof(int), "next_ctu / end_ctu are adjacent");
 constexpr ChainRange CR_DECISION = { offsetof(Chain, dec_state), sizeof(Chain) - offsetof(Chain, dec_state) };      /* dec_state .. the end */
 static_assert(offsetof(Chain, dec_state) > offsetof(Chain, prof) && offsetof(Chain, dec_state) > offsetof(Chain, state), "the decision block lies behind the coder state and the counters");
+/* the label fields alone: binding labels touches neither the decision block in front of them nor the search state inside it */
+constexpr ChainRange CR_LABELS = { offsetof(Chain, labels), sizeof(void *) + 8 * sizeof(int) };      /* labels, lbl_off, lbl_w */
+static_assert(offsetof(Chain, lbl_off) == offsetof(Chain, labels) + sizeof(void *) && offsetof(Chain, lbl_w) == offsetof(Chain, lbl_off) + 4 * sizeof(int)
+              && offsetof(Chain, labels) >= offsetof(Chain, tile_h) + sizeof(int), "labels / lbl_off / lbl_w are adjacent, behind the tile rectangle");
 constexpr ChainRange CR_COL = { offsetof(Chain, col), sizeof(void *) };
 static_assert(sizeof(((Chain *)0)->col) == sizeof(void *), "col is one pointer");
 constexpr ChainRange CR_PU_TRACE = { offsetof(Chain, pu_trace), sizeof(void *) };
@@ -567,6 +586,29 @@ struct HostState {
     }
     for (int k = first; k < i; k++) pic[(size_t)k] = Picture{ first, i - first };
     return i - first;
+  }
+
+  /* ---- the fork's decision block and the caller's labels.  NL: elements of one picture's label array */
+  int label_count() const { return maps_geom(sp.width, sp.height, 0, nullptr).lvl_off[4]; }
+  /* fcu_chain_set_decision: Verifying / Testing predict from the OBF map or from labels bound before; the binding stays */
+  int set_decision(int chain, const fcu_decision_params *dp)
+  {
+    if (!dp || !has(chain)) return refuse(FCU_ERR_ARG, "fcu_chain_set_decision: bad argument");
+    if (dp->state < FCU_TRAINING || dp->state > FCU_TESTING) return refuse(FCU_ERR_ARG, "fcu_chain_set_decision: unknown state");
+    Chain &h = chains[(size_t)chain];
+    if (dp->state != FCU_TRAINING && !dp->dev_obf && !h.labels) return refuse(FCU_ERR_ARG, "fcu_chain_set_decision: Verifying / Testing need the frame's OBF map (fcu_obf_prepass) or labels bound before (fcu_chain_set_labels)");
+    if (const int rc = bound("fcu_chain_set_decision", chain)) return rc;
+    chain_set_decision(h, dp->state, dp->depth_exception, dp->dev_obf, dp->sw_skip2nx2n, dp->sw_terminate);
+    return FCU_OK;
+  }
+  /* fcu_chain_set_labels: null unbinds -- but not from a chain that would then predict from nothing */
+  int set_labels(int chain, const int8_t *labels)
+  {
+    if (const int rc = bound("fcu_chain_set_labels", chain)) return rc;
+    Chain &h = chains[(size_t)chain];
+    if (!labels && h.dec_state != DEC_TRAINING && !h.obf) return refuse(FCU_ERR_STATE, "fcu_chain_set_labels: a chain in the Verifying / Testing state without an OBF map cannot lose its labels (set the state to Training first)");
+    chain_set_labels(h, labels);
+    return FCU_OK;
   }
 
   /* fcu_chain_set_range: the state checks before the range checks */

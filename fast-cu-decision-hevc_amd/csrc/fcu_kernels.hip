@@ -471,15 +471,20 @@ int fcu_get_ctx_state_full(fcu_ctx *c, int chain, uint8_t *ctx176, uint64_t *fra
 
 int fcu_chain_set_decision(fcu_ctx *c, int chain, const fcu_decision_params *dp)
 {
-  if (!c || !dp || !c->hs.has(chain)) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: bad argument");
-  if (dp->state < FCU_TRAINING || dp->state > FCU_TESTING) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: unknown state");
-  if (dp->state != FCU_TRAINING && !dp->dev_obf) return fail(FCU_ERR_ARG, "fcu_chain_set_decision: Verifying / Testing need the frame's OBF map (fcu_obf_prepass)");
-  HOST("", bound("fcu_chain_set_decision", chain));
+  HOST("fcu_chain_set_decision: bad argument", set_decision(chain, dp));
   HIPCHK(hipSetDevice(c->hs.sp.device));
-  chain_set_decision(c->hs.chains[(size_t)chain], dp->state, dp->depth_exception, dp->dev_obf, dp->sw_skip2nx2n, dp->sw_terminate);
   /* only the decision block of the descriptor: the chain's position and context state on the device stay as they are */
   return upload(c, chain, 1, CR_DECISION, true);
 }
+
+int fcu_chain_set_labels(fcu_ctx *c, int chain, const int8_t *dev_labels)
+{
+  HOST("fcu_chain_set_labels: bad argument", set_labels(chain, dev_labels));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  /* only the label fields: the decision block, the search state and everything in front of them on the device stay as they are */
+  return upload(c, chain, 1, CR_LABELS, true);
+}
+int fcu_label_count(const fcu_ctx *c) { return c ? c->hs.label_count() : 0; }
 
 int fcu_chain_set_collocated(fcu_ctx *c, int chain, const fcu_ctu_out *dev_col_out)
 {
@@ -907,6 +912,19 @@ int fcu_decision_maps(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out,
   HIPCHK(ev.record(1));
   HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) is done with */
   if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+/* label arrays from depth / part_size rasters: labels_ctu (fcu_maps.h), one launch for the batch */
+int fcu_labels_from_rasters(fcu_ctx *c, int n_pics, const uint8_t *dev_depth, const int8_t *dev_part_size, int8_t *dev_labels, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_labels_from_rasters: null context");
+  { std::string err; const int rc = labels_args_check(n_pics, dev_depth, dev_labels, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  hipLaunchKernelGGL(labels_ctu, dim3((unsigned)((G.n_ctu + LABELS_CTUS - 1) / LABELS_CTUS), (unsigned)n_pics), dim3(LABELS_THREADS), 0, (hipStream_t)hip_stream,
+                     dev_depth, dev_part_size, dev_labels, G);
+  HIPCHK(hipGetLastError());
   return FCU_OK;
 }
 

@@ -23,16 +23,24 @@
  *               every counter is one wave ballot + popcount, the four waves meet in LDS, threads 0..15 store one dword of the
  *               64-byte record each.
  *   match_pic   one 256-thread workgroup per picture folds the CTU records as report_pic does: 64-bit sums, no atomics.
+ *   labels_ctu  the inverse of the label half of maps_ctu (fcu_labels_from_rasters): the picture-wide depth / part_size rasters in,
+ *               the label array out.  One wave per CTU, four CTUs per 256-thread workgroup, no LDS and no barrier: lane l owns node
+ *               21 + l of the CTU's quadtree (the 64 blocks of level 3) and, l < 21, node l (levels 0..2) as well.  A node reads
+ *               the raster byte(s) at its top-left partition -- byte loads, right at any base address and any W4; the two or four
+ *               loads of a lane are issued before the first is used -- and stores its one label byte.  The label rule is
+ *               maps_label, shared with maps_ctu, so the maps of a decided picture give back the labels maps_ctu wrote.
  * Every output byte is written by exactly one thread; nothing must be cleared beforehand: a repeated call gives identical bytes.
  * Algorithmic bytes per picture: 256 B per CTU and requested array (1 024 B for mv; depth and part_size for the labels when they
  * are not among the arrays: two more rows, of which 85 + 64 bytes are used; 2 B per partition of the OBF map) + the map bytes
- * written.  Split match: 2 x 512 B per CTU + 64 B per CTU written and read back.
+ * written.  Split match: 2 x 512 B per CTU + 64 B per CTU written and read back.  Labels from rasters: 85 B of the depth raster and
+ * 64 B of the part_size raster read per whole CTU, 85 B written.
  */
 #pragma once
 #include "fcu_report.h"
 
 namespace fcu {
 
+enum { LABELS_THREADS = 256, LABELS_CTUS = LABELS_THREADS / 64 };      /* labels_ctu: one wave per CTU */
 enum { MAPS_THREADS = 256, MAPS_NODES = 85, MATCH_COUNTERS = 26, MATCH_CTU_WORDS = 16, MATCH_PIC_AHEAD = 8, MAPS_SIZE_NXN = 3 };
 static_assert(sizeof(fcu_ctu_match) == 4 * MATCH_CTU_WORDS && sizeof(fcu_pic_match) == 8 * MATCH_COUNTERS && MATCH_COUNTERS <= 2 * MATCH_CTU_WORDS,
               "record layouts the word-wise stores rely on");
@@ -247,7 +255,34 @@ __device__ static inline void match_pic_phase(MatchPicLds &L, const fcu_ctu_matc
   }
 }
 
+/* ---- labels_ctu: the whole kernel body (no LDS, no barrier: one phase) */
+__device__ static inline void labels_ctu_body(const uint8_t *depth, const int8_t *part_size, int8_t *labels, const MapsGeom &G)
+{
+  const int l = (int)threadIdx.x & 63, a = (int)blockIdx.x * LABELS_CTUS + ((int)threadIdx.x >> 6), pic = (int)blockIdx.y;
+  if (a >= G.n_ctu) return;                                  /* (a whole wave) */
+  const int cx = a % G.w_ctu, cy = a / G.w_ctu, W4 = G.width >> 2, H4 = G.height >> 2;
+  const size_t plane = (size_t)H4 * W4;
+  const FCU_HBM uint8_t *dp = (const FCU_HBM uint8_t *)depth + (size_t)pic * plane;
+  const FCU_HBM int8_t *pp = part_size ? (const FCU_HBM int8_t *)part_size + (size_t)pic * plane : nullptr;
+  FCU_HBM int8_t *out = (FCU_HBM int8_t *)labels + (size_t)pic * (size_t)G.lvl_off[4];
+  /* node 0: level 3 (every lane), node 1: levels 0..2 (lanes 0..20).  A node that exists has its top-left partition inside the
+   * picture, so every load below is inside the rasters; every store is at idx < lvl_off[4] */
+  MapsNode N[2] = { maps_node(21 + l), maps_node(l < 21 ? l : 0) };
+  MapsPlace P[2] = { maps_place(G, N[0], cx, cy), maps_place(G, N[1], cx, cy) };
+  P[1].exists = P[1].exists && l < 21;
+  int dv[2] = { 0, 0 }, pv = 0;
+#pragma unroll
+  for (int k = 0; k < 2; k++) if (P[k].exists) dv[k] = dp[(size_t)(cy * 16 + N[k].py) * W4 + cx * 16 + N[k].px];
+  if (pp && P[0].exists) pv = pp[(size_t)(cy * 16 + N[0].py) * W4 + cx * 16 + N[0].px];      /* (part_size matters at level 3 alone) */
+#pragma unroll
+  for (int k = 0; k < 2; k++) if (P[k].exists) out[P[k].idx] = (int8_t)maps_label(N[k].d, dv[k], pv, P[k].whole);
+}
+
 #ifndef FCU_EMU
+__global__ void __launch_bounds__(LABELS_THREADS) labels_ctu(const uint8_t *depth, const int8_t *part_size, int8_t *labels, const MapsGeom G)
+{
+  labels_ctu_body(depth, part_size, labels, G);
+}
 template <int UNIT, int ALIGN>
 __global__ void __launch_bounds__(MAPS_THREADS) maps_ctu(const MapsPic *pics, const MapsOut Q, const MapsGeom G)
 {

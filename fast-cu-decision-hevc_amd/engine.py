@@ -182,7 +182,8 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_chain_set_references", "fcu_chain_set_collocated_pocs", "fcu_chain_get_search_state", "fcu_chain_set_search_state",
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
-           "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices"]
+           "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices",
+           "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -278,6 +279,9 @@ def load_lib():
     lib.fcu_hash_string.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int]
     lib.fcu_decision_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_split_match.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_chain_set_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.fcu_label_count.argtypes = [C.c_void_p]
+    lib.fcu_labels_from_rasters.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -623,7 +627,8 @@ class CuEngine:
 
     # -- fork decision hooks of xCompressCU
     def set_decision(self, chain, state, obf=None, sw_skip=(0, 0, 0, 0), sw_term=(0, 0, 0, 0), depth_exception=0):
-        """obf: this frame's map from obf_prepass (int16 tensor [height/4, width/4] on this device)."""
+        """obf: this frame's map from obf_prepass (int16 tensor [height/4, width/4] on this device); None in the Verifying /
+        Testing state: the chain predicts from the labels set_labels bound before."""
         dp = DecisionParams()
         dp.state, dp.depth_exception = state, depth_exception
         for d in range(4):
@@ -633,6 +638,44 @@ class CuEngine:
             dp.dev_obf = obf.data_ptr()
             self._keep_obf[chain] = obf
         self._chk(self.lib.fcu_chain_set_decision(self.h, chain, C.byref(dp)), "fcu_chain_set_decision")
+
+    # -- split labels of a model of the caller's in the place of the Naive label
+    def label_count(self):
+        """NL: elements of one picture's label array (fcu_label_count)"""
+        return self.lib.fcu_label_count(self.h)
+
+    def set_labels(self, chains, labels):
+        """Binds one picture's label array -- an int8 device tensor of label_count() elements in the layout decision_maps writes
+        (the four levels one after the other; LABEL_SPLIT = Skip2Nx2N, LABEL_NOT_SPLIT = TerminateCU, anything else = no
+        prediction) -- to a chain or to every chain of `chains` (the slice, row or tile chains of the picture share the array),
+        in the place of the Naive label on the OBF map; None unbinds (fcu_chain_set_labels).  After set_decision when that
+        names an OBF map; a chain without one takes its labels first and its Verifying / Testing state after."""
+        chains = [chains] if isinstance(chains, int) else list(chains)
+        if labels is not None:
+            assert labels.is_cuda and labels.dtype == self.torch.int8 and labels.is_contiguous() and labels.numel() == self.label_count(), "set_labels: int8 [NL] on the device"
+        for k in chains:
+            self._chk(self.lib.fcu_chain_set_labels(self.h, k, labels.data_ptr() if labels is not None else None), "fcu_chain_set_labels")
+            self._keep_obf[("labels", k)] = labels
+
+    def labels_from_rasters(self, depth, part_size=None, out=None, stream=None):
+        """Label arrays from depth (uint8) and part_size (int8, or None: no NxN) rasters [n, height / 4, width / 4] on the device --
+        the form partition models predict and decision_maps(fields=("depth", "part_size")) writes -- formed on the device
+        (fcu_labels_from_rasters).  Returns the int8 tensor [n, NL] (`out` when given); row i is what set_labels takes."""
+        torch = self.torch
+        H4, W4 = self.height // 4, self.width // 4
+        depth = depth[None] if depth.dim() == 2 else depth
+        n = depth.shape[0]
+        assert depth.is_cuda and depth.dtype == torch.uint8 and depth.is_contiguous() and tuple(depth.shape[1:]) == (H4, W4)
+        if part_size is not None:
+            part_size = part_size[None] if part_size.dim() == 2 else part_size
+            assert part_size.is_cuda and part_size.dtype in (torch.int8, torch.uint8) and part_size.is_contiguous() and tuple(part_size.shape) == (n, H4, W4)
+        if out is None:
+            out = torch.empty((n, self.label_count()), dtype=torch.int8, device=depth.device)
+        assert out.is_cuda and out.dtype == torch.int8 and out.is_contiguous() and out.numel() == n * self.label_count()
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_labels_from_rasters(self.h, n, depth.data_ptr(), part_size.data_ptr() if part_size is not None else None, out.data_ptr(), s),
+                  "fcu_labels_from_rasters")
+        return out
 
     def verify_counts(self, first, n=1):
         v = VerifyCounts()

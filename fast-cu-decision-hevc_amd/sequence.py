@@ -96,8 +96,15 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, **flags):
-        """slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, **flags):
+        """labels (with fast=True): a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None -- a partition model of the
+        caller's in the place of the Naive label.  It is asked for every Verifying and Testing picture with the picture's index, its
+        source planes (Y, U, V device tensors) and its OBF map (device tensor); the label array it returns (the layout
+        CuEngine.decision_maps writes; CuEngine.labels_from_rasters makes one from depth / part_size rasters) is bound to every
+        chain of the picture (CuEngine.set_labels): counted on Verifying pictures -- the switches come from fcu_decision_switch on
+        those counts exactly as for the Naive label --, pruning on Testing pictures.  None: the picture uses N_OBF as before.  The
+        result dict of a picture that ran on labels carries them as `labels`.
+        slice_ctus: CTUs per slice (HM's SliceMode 1 / SliceArgument).  None = one slice per picture, which is the
         reference's default (SliceMode 0, TAppEncCfg.cpp:838) and what `encoder_intra_main.cfg` encodes; a smaller value
         (e.g. the picture width in CTUs for one slice per CTU row) is a DIFFERENT encoder configuration -- the slices then
         run as concurrent chains, but every slice start cuts the intra neighbourhood and resets CABAC.
@@ -122,6 +129,9 @@ class SequenceDecider:
         split-label maps; a picture that was decided with an OBF map (fast=True, outside Training) also gets `n_obf`.  They are
         formed after the launch, one batched call per group."""
         self.do_report = report
+        if labels is not None and not callable(labels):
+            raise ValueError("SequenceDecider: labels is a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None")
+        self.labels = labels
         self.maps = engine_maps_options(maps, ("depth", "part_size", "pred_mode", "intra_dir_luma"), "SequenceDecider")
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
@@ -168,7 +178,12 @@ class SequenceDecider:
                 obf = eng.obf_prepass(eng.org_planes(first)[0])[0][0].contiguous()
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
+                lab = self.labels(poc, eng.org_planes(first), obf) if self.labels is not None else None
+                if lab is not None:                            # labels are per picture: every chain of it takes the one array
+                    eng.set_labels(range(first, first + n_sl), lab)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
+            if state != TRAINING and lab is not None:
+                pics[-1]["labels"] = lab
             if self.maps and state != TRAINING:
                 pics[-1]["obf"] = obf
         eng.compress_pictures(0, len(yuvs), self.layout)

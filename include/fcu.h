@@ -45,6 +45,9 @@
  *   calcMD5 / calcCRC / calcChecksum,               fcu_picture_hash (the decoded-picture hash of reconstructed pictures, per
  *     digestToString (TComPicYuvMD5.cpp:44-225,       plane, as the encoder prints it at the end of the picture line),
  *      TEncGOP.cpp:1619-1640,1742-1756)               fcu_hash_string (the printed form)
+ *   the fork's other model types (SVM, forest,      fcu_chain_set_labels (split labels of a model of the caller's, per picture, in
+ *     CNN ... behind the same hooks,                  the place of the Naive label), fcu_label_count, fcu_labels_from_rasters
+ *     tools_YS.cpp:686-695, TEncCu.cpp:670-678)       (depth / part_size rasters -> label array)
  *   the published decision as pictures;             fcu_decision_maps (raster maps of the per-partition arrays of fcu_ctu_out, the
  *     the fork's Training dump of split labels         motion map, per-CU split labels and N_OBF features of the chosen tree),
  *     next to N_OBF (tools_YS.cpp:304-318,             fcu_split_match (agreement of two decisions of a picture, per partition
@@ -521,6 +524,40 @@ typedef struct fcu_pic_match { uint64_t part_total, part_equal, node[4][2][2], o
  * entry of one, NULL host_matches. */
 int  fcu_split_match(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b,
                      fcu_pic_match *host_matches, fcu_ctu_match *dev_ctu, float *kernel_ms2, void *hip_stream);
+
+/* ---- caller-supplied split labels: a model of the caller's in the place of the Naive model on N_OBF.  The engine's only predictor is
+ * "N_OBF > 0" on the OBF map; a caller that trained another model on the label maps of fcu_decision_maps runs it wherever it likes
+ * and hands its prediction back as ONE label array per picture, int8 [NL] in the layout of the label maps above, in HBM:
+ *   FCU_LABEL_SPLIT      the fork's Skip2Nx2N label ("will be divided")
+ *   FCU_LABEL_NOT_SPLIT  its TerminateCU label
+ *   any other value (FCU_LABEL_ABSENT and FCU_LABEL_FORCED among them): no prediction -- the CU is searched exhaustively and is
+ *                        not counted in the Verifying state.
+ * A CU of depth d at luma (x, y) reads element off(d) + (y / s) * BW(d) + x / s, s = 64 >> d: picture coordinates, so the slice
+ * chains, WaveFrontSynchro rows and tile chains of a picture all take the picture's one array.  A CU the picture edge cuts reads no
+ * label (it is split without a decision, as before).  Everything else of the decision block stays as fcu_chain_set_decision set
+ * it: the state, sw_skip2nx2n / sw_terminate per depth, and depth_exception, which with labels bound reads "no pruning of depth-3
+ * CUs labelled FCU_LABEL_SPLIT".  The label array an OBF map would give (N_OBF > 0 -> SPLIT, else NOT_SPLIT) decides bit for bit
+ * what that OBF map decides.
+ * fcu_chain_set_labels binds dev_labels (fcu_label_count() bytes, kept alive and unchanged by the caller while the chain runs) to a
+ * bound chain, NULL unbinds; fcu_chain_begin and the picture binders start a chain without labels, fcu_chain_set_decision leaves
+ * the binding as it is.  With labels bound the OBF map is never read, and fcu_chain_set_decision accepts FCU_VERIFYING / FCU_TESTING
+ * with a NULL dev_obf.  Call order: after fcu_chain_set_decision when that call names an OBF map (the labels then take its place);
+ * without an OBF map bind the labels while the chain is in FCU_TRAINING -- the state fcu_chain_begin leaves -- and set the state
+ * after.  Only the label fields of the descriptor are copied: position, coder state, counters and search state on the device stay.
+ * FCU_ERR_ARG: a bad chain index; FCU_ERR_STATE: a chain that is not bound, and unbinding (NULL) from a chain in FCU_VERIFYING /
+ * FCU_TESTING that has no OBF map (it would have nothing to predict from). */
+int  fcu_chain_set_labels(fcu_ctx *c, int chain, const int8_t *dev_labels);
+/* NL of this context's picture size: elements of one picture's label array (and of its N_OBF maps) */
+int  fcu_label_count(const fcu_ctx *c);
+/* Label arrays from rasters: the inverse of the label half of fcu_decision_maps.  dev_depth: uint8 [n_pics][H4][W4], the CU depth per
+ * 4x4 partition (the byte map FCU_MAP_DEPTH; the form partition models predict); dev_part_size: int8 [n_pics][H4][W4] (FCU_MAP_PART_SIZE)
+ * or NULL; dev_labels: int8 [n_pics][NL].  Block (by, bx) of level d looks at the partition at its top-left corner: depth < d ->
+ * FCU_LABEL_ABSENT; else, d < 3 and the block not wholly inside the picture -> FCU_LABEL_FORCED; else d < 3: depth > d -> FCU_LABEL_SPLIT,
+ * depth == d -> FCU_LABEL_NOT_SPLIT; d = 3: part_size NxN (3) -> FCU_LABEL_SPLIT, else (and always with a NULL dev_part_size)
+ * FCU_LABEL_NOT_SPLIT.  On the maps of a decided picture this gives the bytes fcu_decision_maps gives.  All three arrays may start at
+ * any byte.  Every output byte is written by exactly one thread, no atomics, nothing to clear: the same input gives the same bytes.
+ * One kernel on `hip_stream`, asynchronous.  FCU_ERR_ARG: n_pics < 1, a NULL dev_depth or dev_labels. */
+int  fcu_labels_from_rasters(fcu_ctx *c, int n_pics, const uint8_t *dev_depth, const int8_t *dev_part_size, int8_t *dev_labels, void *hip_stream);
 
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
