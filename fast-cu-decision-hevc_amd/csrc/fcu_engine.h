@@ -312,6 +312,10 @@ struct Chain {
    * them alone (CR_LABELS, fcu_host.h). */
   const int8_t *labels;
   int lbl_off[4], lbl_w[4];
+  /* Optional [n_ctu][FCU_CUS_PER_CTU] record of both RD costs of every CU the search visits (fcu_chain_set_cu_trace), written by
+   * the host only; the chains of a picture share one array and write disjoint CTUs.  The last field of the GPU layout, behind
+   * everything the CR_* ranges of fcu_host.h name: binding it copies this pointer alone (CR_CU_TRACE). */
+  fcu_cu_trace *cu_trace;
 #ifdef FCU_EMU
   /* emulator only (the GPU layout has neither): bit r of wpp_mv_known = int_mv_r[r] holds HM's value (written by this row's
    * search, or taken from the caller / the row above); wpp_mv_rbw counts TZ searches that read a slot before it was known */
@@ -3519,6 +3523,7 @@ FCU_DEV FCU_NOINLINE void compress_cu()
   /* predictSkip: 1 = the label Skip2Nx2N, 0 = TerminateCU, -1 = no prediction (a caller's label array may leave a CU open: it is
    * searched exhaustively and not counted).  The Naive model always predicts. */
   int skip2Nx2N = 0, earlyTerminate = 0, predictSkip = -1;
+  int nxnTried = 0;                                          /* (D == MAXDEPTH only) */
   if (!boundary && state != DEC_TRAINING) {
     predictSkip = E.C->labels ? cu_label<D>(E.C, x, y) : (cu_num_obf(x, y, s) > 0);
     if (state == DEC_TESTING && predictSkip >= 0) {          /* TEncCu.cpp:951-996 */
@@ -3576,7 +3581,8 @@ FCU_DEV FCU_NOINLINE void compress_cu()
       check_rd_cost_intra(D, SIZE_NxN);
       FCU_SERIAL { g_S.dec_flip ^= g_S.best_idx[D]; g_S.dec_j1 = g_S.dec_flip ? cu_best(E, D)->cost : cu_temp(E, D)->cost; }   /* :1175-1183 */
       cu_init(cu_temp(E, D), D, x, y, zidx);
-    } else if (D == MAXDEPTH && state == DEC_VERIFYING) {    /* NxN not tried (a P CU whose best inter candidate has no residual): */
+      nxnTried = 1;
+    } else if (D == MAXDEPTH && (state == DEC_VERIFYING || FCU_UNI(E.C->cu_trace) != nullptr)) {    /* NxN not tried (a P CU whose best inter candidate has no residual; Testing: TerminateCU): */
       FCU_SERIAL { g_S.dec_j0 = cu_best(E, D)->cost; g_S.dec_j1 = 0; g_S.dec_flip = 0; }      /* J1 0, bPartition_True false, not what the CU before left */
     }
     FCU_SERIAL {
@@ -3629,6 +3635,19 @@ FCU_DEV FCU_NOINLINE void compress_cu()
   }
   if (!boundary && state == DEC_VERIFYING && predictSkip >= 0) {      /* TEncCu.cpp:1489-1497 */
     FCU_SERIAL count_verify(E.C, D, predictSkip, g_S.dec_flip, g_S.dec_j0, g_S.dec_j1);
+  }
+  /* fcu_cu_trace of this CU: the numbers count_verify takes, in every state (the pointer is read here, not kept across the
+   * sub-CUs: with no trace bound the cost is this wave-uniform branch) */
+  fcu_cu_trace *const trace = boundary ? (fcu_cu_trace *)nullptr : FCU_UNI(E.C->cu_trace);
+  if (trace) {
+    const int splitTried = D < MAXDEPTH ? !earlyTerminate : nxnTried;      /* the four sub-CUs were searched / SIZE_NxN was tried */
+    FCU_SERIAL {
+      FCU_HBM fcu_cu_trace *r = (FCU_HBM fcu_cu_trace *)trace + (size_t)E.cur_ctu * FCU_CUS_PER_CTU + pu_trace_index(D, 0, zidx);
+      /* a CU that was not divided (D < 3, Testing: TerminateCU) never set dec_j0: its whole-CU cost with the split flag is the best cost */
+      const double j0 = (splitTried || D == MAXDEPTH) ? g_S.dec_j0 : cu_best(E, D)->cost;
+      r->j0 = j0; r->j1 = splitTried ? g_S.dec_j1 : 0.0;
+      r->valid = 1; r->split_won = (uint8_t)(splitTried && g_S.dec_flip); r->whole_tried = (uint8_t)(j0 != FCU_MAX_DOUBLE); r->split_tried = (uint8_t)splitTried;
+    }
   }
   cu_copy_to_pic(cu_best(E, D));
   copy_reco_to_pic(&G->reco[D][g_S.reco_best_idx[D]], x, y, s);
@@ -3746,6 +3765,10 @@ FCU_DEV FCU_NOINLINE void compress_ctu(Chain *C, Scratch *G, int pos)
     for (int i = lane; i < 1024; i += 64) { out->coeff_cb[i] = 0; out->coeff_cr[i] = 0; }
     cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, 0, CI_CURR_BEST), lane);
     if (lane == 0) { for (int d = 0; d < 4; d++) { g_S.best_idx[d] = 0; g_S.reco_best_idx[d] = 0; } G->par_ps[0] = SIZE_NONE; out->total_cost = FCU_MAX_DOUBLE; out->total_dist = out->total_bits = out->total_bins = 0; }
+  }
+  if (FCU_UNI(C->cu_trace) != nullptr) {                     /* the CTU's 85 records start as "not visited": 2040 bytes, lanes striding */
+    FCU_HBM uint32_t *w = (FCU_HBM uint32_t *)(C->cu_trace + (size_t)ctuRsAddr * FCU_CUS_PER_CTU);
+    FCU_FOR_LANES { for (int i = lane; i < (int)(FCU_CUS_PER_CTU * sizeof(fcu_cu_trace) / 4); i += 64) w[i] = 0u; }
   }
   cu_init(&G->cu[0][0], 0, x, y, 0);
   cu_init(&G->cu[0][1], 0, x, y, 0);

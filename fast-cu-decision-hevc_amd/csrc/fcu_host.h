@@ -388,6 +388,36 @@ inline int labels_args_check(int n_pics, const void *dev_depth, const void *dev_
   if (bad) { err = std::string("fcu_labels_from_rasters: ") + bad; return FCU_ERR_ARG; }
   return FCU_OK;
 }
+/* fcu_label_score / fcu_trace_maps: what they refuse, with the argument named; FCU_OK otherwise */
+inline int score_args_check(int n_pics, const fcu_cu_trace *const *dev_trace, const int8_t *const *dev_labels, const fcu_pic_score *host_scores, std::string &err)
+{
+  const std::string who = "fcu_label_score: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_trace) bad = "dev_trace is null";
+  else if (!dev_labels) bad = "dev_labels is null";
+  else if (!host_scores) bad = "host_scores is null";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < n_pics; i++) {
+    if (!dev_trace[i]) { err = who + "dev_trace[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+    if (!dev_labels[i]) { err = who + "dev_labels[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  }
+  return FCU_OK;
+}
+inline int trace_maps_args_check(int n_pics, const fcu_cu_trace *const *dev_trace, const void *dev_labels, const void *dev_j0, const void *dev_j1, std::string &err)
+{
+  const std::string who = "fcu_trace_maps: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_trace) bad = "dev_trace is null";
+  else if (!dev_labels && !dev_j0 && !dev_j1) bad = "no output is wanted (dev_labels, dev_j0 and dev_j1 null)";
+  else if (((uintptr_t)dev_j0 | (uintptr_t)dev_j1) & 7) bad = "dev_j0 and dev_j1 start at multiples of 8 bytes";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < n_pics; i++) if (!dev_trace[i]) { err = who + "dev_trace[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+/* fcu_cu_index: the record of the CU of `depth` whose first 4x4 partition is zidx (z-order) inside its CTU's FCU_CUS_PER_CTU */
+inline int cu_index(int depth, int zidx) { return depth <= 0 ? 0 : depth == 1 ? 1 + (zidx >> 6) : depth == 2 ? 5 + (zidx >> 4) : 21 + (zidx >> 2); }
 /* the unit the rows of the byte maps (and of the motion map) go out in: 16 bytes when every row of every map starts on 16 bytes
  * -- W4 a multiple of 16 (whole CTU columns, every map a multiple of 16 bytes) and aligned bases --, else 2-byte units, which
  * W4 even always allows; their alignment is the base's: 2, or 1 for a byte map at an odd address */
@@ -459,6 +489,11 @@ constexpr ChainRange CR_COL = { offsetof(Chain, col), sizeof(void *) };
 static_assert(sizeof(((Chain *)0)->col) == sizeof(void *), "col is one pointer");
 constexpr ChainRange CR_PU_TRACE = { offsetof(Chain, pu_trace), sizeof(void *) };
 static_assert(sizeof(((Chain *)0)->pu_trace) == sizeof(void *), "pu_trace is one pointer");
+/* the CU trace: the last pointer of the GPU layout, behind every range above -- binding it copies that pointer alone */
+constexpr ChainRange CR_CU_TRACE = { offsetof(Chain, cu_trace), sizeof(void *) };
+static_assert(sizeof(((Chain *)0)->cu_trace) == sizeof(void *) && offsetof(Chain, cu_trace) == CR_LABELS.off + CR_LABELS.len
+              && offsetof(Chain, cu_trace) >= offsetof(Chain, int_mv_r) + sizeof(((Chain *)0)->int_mv_r) && CR_DECISION.off + CR_DECISION.len >= CR_CU_TRACE.off + CR_CU_TRACE.len,
+              "cu_trace is one pointer directly behind the label fields; the decision copy, which runs to the end, carries the host's copy of it");
 constexpr ChainRange CR_INT_MV = { offsetof(Chain, int_mv_r), 2 * FCU_MAX_REF * sizeof(int32_t) };
 static_assert(sizeof(((Chain *)0)->int_mv_r) == 2 * FCU_MAX_REF * sizeof(int32_t), "search state layout");
 
@@ -608,6 +643,22 @@ struct HostState {
     Chain &h = chains[(size_t)chain];
     if (!labels && h.dec_state != DEC_TRAINING && !h.obf) return refuse(FCU_ERR_STATE, "fcu_chain_set_labels: a chain in the Verifying / Testing state without an OBF map cannot lose its labels (set the state to Training first)");
     chain_set_labels(h, labels);
+    return FCU_OK;
+  }
+
+  /* fcu_chain_set_pu_trace / fcu_chain_set_cu_trace: a bound chain; null stops recording.  The CU trace is cleared and written in
+   * 4- and 8-byte units */
+  int set_pu_trace(int chain, fcu_pu_trace *trace)
+  {
+    if (const int rc = bound("fcu_chain_set_pu_trace", chain)) return rc;
+    chains[(size_t)chain].pu_trace = trace;
+    return FCU_OK;
+  }
+  int set_cu_trace(int chain, fcu_cu_trace *trace)
+  {
+    if (const int rc = bound("fcu_chain_set_cu_trace", chain)) return rc;
+    if ((uintptr_t)trace & 7) return refuse(FCU_ERR_ARG, "fcu_chain_set_cu_trace: dev_trace must start at a multiple of 8 bytes");
+    chains[(size_t)chain].cu_trace = trace;
     return FCU_OK;
   }
 

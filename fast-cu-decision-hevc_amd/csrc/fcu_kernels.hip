@@ -22,6 +22,7 @@
 #include "fcu_report.h"
 #include "fcu_hash.h"
 #include "fcu_maps.h"
+#include "fcu_trace.h"
 
 using namespace fcu;
 
@@ -119,6 +120,7 @@ struct fcu_ctx {
   DevBuf sao;                      /* fcu_sao: picture descriptors, copy of the deblocked planes, statistics, candidates, reconstructed parameters, off counters */
   DevBuf rep;                      /* fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   DevBuf hash;                     /* fcu_picture_hash: plane pointers, hash records, per-chunk partials */
+  DevBuf score;                    /* fcu_label_score / fcu_trace_maps: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   DevBuf maps;                     /* fcu_decision_maps / fcu_split_match: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
    * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
@@ -200,6 +202,9 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_PIC_HASH: return (int)sizeof(fcu_pic_hash);
   case FCU_ABI_CTU_MATCH: return (int)sizeof(fcu_ctu_match);
   case FCU_ABI_PIC_MATCH: return (int)sizeof(fcu_pic_match);
+  case FCU_ABI_CU_TRACE: return (int)sizeof(fcu_cu_trace);
+  case FCU_ABI_CTU_SCORE: return (int)sizeof(fcu_ctu_score);
+  case FCU_ABI_PIC_SCORE: return (int)sizeof(fcu_pic_score);
   default: return -1;
   }
 }
@@ -234,7 +239,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p); hipFree(c->score.p);
   hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
@@ -498,10 +503,17 @@ int fcu_chain_set_collocated(fcu_ctx *c, int chain, const fcu_ctu_out *dev_col_o
 int fcu_pu_index(int depth, int nxn, int zidx) { return nxn ? 85 + zidx : (depth <= 0 ? 0 : depth == 1 ? 1 + (zidx >> 6) : depth == 2 ? 5 + (zidx >> 4) : 21 + (zidx >> 2)); }
 int fcu_chain_set_pu_trace(fcu_ctx *c, int chain, fcu_pu_trace *dev_trace)
 {
-  HOST("fcu_chain_set_pu_trace: bad argument", bound("fcu_chain_set_pu_trace", chain));
+  HOST("fcu_chain_set_pu_trace: bad argument", set_pu_trace(chain, dev_trace));
   HIPCHK(hipSetDevice(c->hs.sp.device));
-  c->hs.chains[(size_t)chain].pu_trace = dev_trace;
   return upload(c, chain, 1, CR_PU_TRACE, true);
+}
+int fcu_cu_index(int depth, int zidx) { return cu_index(depth, zidx); }
+int fcu_chain_set_cu_trace(fcu_ctx *c, int chain, fcu_cu_trace *dev_trace)
+{
+  HOST("fcu_chain_set_cu_trace: bad argument", set_cu_trace(chain, dev_trace));
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  /* only the pointer: position, coder state, counters, search state and labels on the device stay as they are */
+  return upload(c, chain, 1, CR_CU_TRACE, true);
 }
 
 int fcu_get_verify_counts(fcu_ctx *c, int first, int n, fcu_verify_counts *host_sum)
@@ -957,6 +969,60 @@ int fcu_split_match(fcu_ctx *c, int n_pics, const fcu_ctu_out *const *dev_out_a,
   HIPCHK(hipMemcpyAsync(host_matches, d_rec, sizeof(fcu_pic_match) * n_pics, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and host_matches are done with */
   if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
+  return FCU_OK;
+}
+
+/* the Verifying counters of label arrays against CU traces: score_ctu + score_pic (fcu_trace.h), the records back */
+int fcu_label_score(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace, const int8_t *const *dev_labels, fcu_pic_score *host_scores,
+                    fcu_ctu_score *dev_ctu, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_label_score: null context");
+  { std::string err; const int rc = score_args_check(n_pics, dev_trace, dev_labels, host_scores, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const size_t o_pics = 0, o_rec = up(o_pics + sizeof(ScorePic) * n_pics), o_ctu = up(o_rec + sizeof(fcu_pic_score) * n_pics),
+               total = dev_ctu ? o_ctu : up(o_ctu + sizeof(fcu_ctu_score) * (size_t)G.n_ctu * n_pics);
+  HIPCHK(c->score.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->score.p;
+  ScorePic *d_pics = (ScorePic *)(base + o_pics); fcu_pic_score *d_rec = (fcu_pic_score *)(base + o_rec);
+  fcu_ctu_score *d_ctu = dev_ctu ? dev_ctu : (fcu_ctu_score *)(base + o_ctu);
+  std::vector<ScorePic> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) { hp[i].trace = dev_trace[i]; hp[i].labels = dev_labels[i]; }
+  HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(ScorePic) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(score_ctu, dim3((unsigned)((G.n_ctu + SCORE_CTUS - 1) / SCORE_CTUS), (unsigned)n_pics), dim3(SCORE_THREADS), 0, st, d_pics, d_ctu, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  hipLaunchKernelGGL(score_pic, dim3((unsigned)n_pics), dim3(SCORE_PIC_THREADS), 0, st, d_ctu, d_rec, G.n_ctu);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(2));
+  HIPCHK(hipMemcpyAsync(host_scores, d_rec, sizeof(fcu_pic_score) * n_pics, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) and host_scores are done with */
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
+  return FCU_OK;
+}
+
+/* CU traces as label / J0 / J1 maps: trace_ctu (fcu_trace.h), one launch for the batch */
+int fcu_trace_maps(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace, int8_t *dev_labels, double *dev_j0, double *dev_j1, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_trace_maps: null context");
+  { std::string err; const int rc = trace_maps_args_check(n_pics, dev_trace, dev_labels, dev_j0, dev_j1, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  HIPCHK(c->score.reserve(up(sizeof(void *) * n_pics), st));
+  const fcu_cu_trace **d_tr = (const fcu_cu_trace **)c->score.p;
+  HIPCHK(hipMemcpyAsync(d_tr, dev_trace, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  const TraceOut Q = { dev_labels, dev_j0, dev_j1 };
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(trace_ctu, dim3((unsigned)((G.n_ctu + SCORE_CTUS - 1) / SCORE_CTUS), (unsigned)n_pics), dim3(SCORE_THREADS), 0, st, d_tr, Q, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));                          /* dev_trace (the caller's array) is done with */
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
   return FCU_OK;
 }
 

@@ -183,13 +183,27 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_wpp_begin", "fcu_wpp_rows", "fcu_compress_wpp", "fcu_wpp_begin_p", "fcu_wpp_begin_slices",
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
            "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices",
-           "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters"]
+           "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters",
+           "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
 PUS_PER_CTU = 341
 PU_TRACE_DTYPE = np.dtype([("valid", np.uint8), ("best_mode", np.uint8), ("n_rmd", np.uint8), ("n_rd", np.uint8), ("rd_mode", np.uint8, (12,)),
                            ("best_dist", np.uint32), ("pad", np.uint32), ("best_cost", np.float64), ("rmd_cost", np.float64, (8,))])   # fcu_pu_trace
+
+
+CUS_PER_CTU = 85                                           # FCU_CUS_PER_CTU: 1 + 4 + 16 + 64 CUs of depth 0..3
+MAX_DOUBLE = 1.7e+308                                      # FCU_MAX_DOUBLE: j0 of a CU whose whole-CU check was pruned
+CU_TRACE_DTYPE = np.dtype([("j0", np.float64), ("j1", np.float64), ("valid", np.uint8), ("split_won", np.uint8), ("whole_tried", np.uint8),
+                           ("split_tried", np.uint8), ("pad", np.uint8, (4,))])                                                    # fcu_cu_trace
+CTU_SCORE_DTYPE = np.dtype([("n", np.uint16, (4, 4)), ("open", np.uint16, (4,)), ("pad", np.uint16, (12,)), ("loss", np.float64, (4, 2))])   # fcu_ctu_score
+PIC_SCORE_DTYPE = np.dtype([("v", np.float64, (4, 6)), ("open", np.uint32, (4,)), ("scored", np.uint32, (4,))])                    # fcu_pic_score
+
+
+def cu_index(depth, zidx):
+    """fcu_cu_index: position of a CU inside its CTU's 85 records (zidx = z-order index of its first 4x4 partition)"""
+    return load_lib().fcu_cu_index(depth, zidx)
 
 
 def pu_index(depth, nxn, zidx):
@@ -282,6 +296,10 @@ def load_lib():
     lib.fcu_chain_set_labels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.fcu_label_count.argtypes = [C.c_void_p]
     lib.fcu_labels_from_rasters.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fcu_cu_index.argtypes = [C.c_int, C.c_int]
+    lib.fcu_chain_set_cu_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.fcu_label_score.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_trace_maps.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
     _lib = lib
     return lib
 
@@ -695,6 +713,80 @@ class CuEngine:
 
     def pu_trace_array(self, trace):
         return trace.cpu().numpy().view(PU_TRACE_DTYPE).reshape(self.n_ctu, PUS_PER_CTU)
+
+    # -- both RD costs of every CU the search visits (the fork's Training set), and what is made of them on the device
+    def enable_cu_trace(self, chain, trace=None):
+        """Binds a device array of n_ctu x 85 fcu_cu_trace records to the chain (the slice, row or tile chains of a picture share
+        one: pass the tensor the first call returned).  The engine clears a CTU's records when it starts the CTU.  Returns the uint8
+        tensor; cu_trace_array() turns it into a structured numpy array."""
+        torch = self.torch
+        if trace is None:
+            trace = torch.zeros(self.n_ctu * CUS_PER_CTU * CU_TRACE_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        assert trace.is_cuda and trace.dtype == torch.uint8 and trace.is_contiguous() and trace.numel() >= self.n_ctu * CUS_PER_CTU * CU_TRACE_DTYPE.itemsize
+        self._chk(self.lib.fcu_chain_set_cu_trace(self.h, chain, trace.data_ptr()), "fcu_chain_set_cu_trace")
+        self._keep_obf[("cu_trace", chain)] = trace
+        return trace
+
+    def disable_cu_trace(self, chain):
+        self._chk(self.lib.fcu_chain_set_cu_trace(self.h, chain, None), "fcu_chain_set_cu_trace")
+        self._keep_obf.pop(("cu_trace", chain), None)
+
+    def cu_trace_array(self, trace):
+        return trace.cpu().numpy()[:self.n_ctu * CUS_PER_CTU * CU_TRACE_DTYPE.itemsize].view(CU_TRACE_DTYPE).reshape(self.n_ctu, CUS_PER_CTU)
+
+    def _trace_ptrs(self, traces, who):
+        ptrs = (C.c_void_p * max(len(traces), 1))()
+        for i, t in enumerate(traces):
+            t = t["cu_trace"] if isinstance(t, dict) else t
+            assert t.is_cuda and t.dtype == self.torch.uint8 and t.is_contiguous() and t.numel() >= self.n_ctu * CUS_PER_CTU * CU_TRACE_DTYPE.itemsize, who
+            ptrs[i] = t.data_ptr()
+        return ptrs
+
+    def label_score(self, traces, labels, ctu=False, timed=False, stream=None):
+        """The Verifying counters of label arrays against the CU traces of exhaustively decided pictures, without deciding them
+        again (fcu_label_score).  traces: list of trace tensors (enable_cu_trace; result dicts with "cu_trace" qualify); labels:
+        an int8 device tensor [n, NL] or a list of [NL] tensors, picture i against trace i (the layout set_labels takes).
+        Returns a structured array [n] of PIC_SCORE_DTYPE: v [4, 6] = TP, FP, TN, FN, FPLoss, FNLoss per depth (what
+        decision_switch takes), open [4] (samples whose label is no prediction), scored [4].  ctu=True: also the per-CTU records
+        [n, n_ctu] of CTU_SCORE_DTYPE; timed=True: also the durations (ms) of the two kernels.  The extras follow in that order."""
+        torch = self.torch
+        n = len(traces)
+        labs = [labels[i] for i in range(n)]
+        assert len(labels) == n
+        for t in labs:
+            assert t.is_cuda and t.dtype == torch.int8 and t.is_contiguous() and t.numel() == self.label_count(), "label_score: int8 [NL] on the device"
+        tp = self._trace_ptrs(traces, "label_score")
+        lp = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in labs])
+        rec = np.zeros(max(n, 1), PIC_SCORE_DTYPE)
+        d_ctu = torch.empty((n, self.n_ctu, CTU_SCORE_DTYPE.itemsize), dtype=torch.uint8, device=torch.device("cuda", self.device)) if ctu else None
+        ms = (C.c_float * 2)() if timed else None
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_label_score(self.h, n, tp, lp, rec.ctypes.data, d_ctu.data_ptr() if ctu else None, ms, s), "fcu_label_score")
+        rec = rec[:n]
+        if not ctu and not timed:
+            return rec
+        extra = ([d_ctu.cpu().numpy().view(CTU_SCORE_DTYPE).reshape(n, self.n_ctu)] if ctu else []) + ([(ms[0], ms[1])] if timed else [])
+        return (rec, *extra)
+
+    def trace_maps(self, traces, labels=True, costs=False, timed=False, stream=None):
+        """CU traces as the fork's whole Training set, in the layout of the label / N_OBF maps of decision_maps, formed on the
+        device (fcu_trace_maps).  Returns a dict of device tensors over the batch: "labels" (labels=True) int8 [n, NL] --
+        LABEL_SPLIT / LABEL_NOT_SPLIT for every CU the search visited and tried to split, LABEL_ABSENT for the others, LABEL_FORCED
+        where the picture edge cuts the block --, "j0" / "j1" (costs=True) float64 [n, NL], 0.0 where there is no label.  Element
+        for element aligned with decision_maps(...)["n_obf"] flattened.  timed=True: (dict, kernel ms)."""
+        torch = self.torch
+        n, NL = len(traces), self.label_count()
+        dev = torch.device("cuda", self.device)
+        tp = self._trace_ptrs(traces, "trace_maps")
+        d_lab = torch.empty((n, NL), dtype=torch.int8, device=dev) if labels else None
+        d_j0 = torch.empty((n, NL), dtype=torch.float64, device=dev) if costs else None
+        d_j1 = torch.empty((n, NL), dtype=torch.float64, device=dev) if costs else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_trace_maps(self.h, n, tp, ptr(d_lab), ptr(d_j0), ptr(d_j1), C.byref(ms) if timed else None, s), "fcu_trace_maps")
+        res = {k: v for k, v in (("labels", d_lab), ("j0", d_j0), ("j1", d_j1)) if v is not None}
+        return (res, float(ms.value)) if timed else res
 
     # -- TComLoopFilter::loopFilterPic
     def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1, slice_ctus=None, lf_cross_slices=1, layout=None):

@@ -96,8 +96,11 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, **flags):
-        """labels (with fast=True): a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None -- a partition model of the
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, cu_trace=False, **flags):
+        """cu_trace=True: every Training picture (all of them with fast=False) is decided with a CU trace bound to its chains
+        (CuEngine.enable_cu_trace): its result dict gains `cu_trace`, the device tensor of n_ctu x 85 fcu_cu_trace records -- J0, J1 and
+        the outcome of every CU the exhaustive search visited; CuEngine.trace_maps and CuEngine.label_score take it as it is.
+        labels (with fast=True): a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None -- a partition model of the
         caller's in the place of the Naive label.  It is asked for every Verifying and Testing picture with the picture's index, its
         source planes (Y, U, V device tensors) and its OBF map (device tensor); the label array it returns (the layout
         CuEngine.decision_maps writes; CuEngine.labels_from_rasters makes one from depth / part_size rasters) is bound to every
@@ -132,6 +135,7 @@ class SequenceDecider:
         if labels is not None and not callable(labels):
             raise ValueError("SequenceDecider: labels is a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None")
         self.labels = labels
+        self.cu_trace = bool(cu_trace)
         self.maps = engine_maps_options(maps, ("depth", "part_size", "pred_mode", "intra_dir_luma"), "SequenceDecider")
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
@@ -182,6 +186,11 @@ class SequenceDecider:
                 if lab is not None:                            # labels are per picture: every chain of it takes the one array
                     eng.set_labels(range(first, first + n_sl), lab)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
+            if self.cu_trace and state == TRAINING:            # one array per picture, shared by its chains; the result owns it
+                tr = eng.enable_cu_trace(first)
+                for k in range(1, n_sl):
+                    eng.enable_cu_trace(first + k, tr)
+                pics[-1]["cu_trace"] = tr
             if state != TRAINING and lab is not None:
                 pics[-1]["labels"] = lab
             if self.maps and state != TRAINING:

@@ -52,6 +52,10 @@
  *     the fork's Training dump of split labels         motion map, per-CU split labels and N_OBF features of the chosen tree),
  *     next to N_OBF (tools_YS.cpp:304-318,             fcu_split_match (agreement of two decisions of a picture, per partition
  *      TEncCu.cpp:585-600,1489-1497)                   and per quadtree node)
+ *   the fork's Training set of ALL visited CUs:      fcu_chain_set_cu_trace (J0, J1 and the outcome of every CU the search visits, kept
+ *     label, J0, J1 per CU (tools_YS.cpp:304-318,     per CTU), fcu_trace_maps (the trace as label / J0 / J1 maps aligned with N_OBF),
+ *      968-986; TEncCu.cpp:1450-1451,1489-1497)       fcu_label_score (countTFPN + countRDLoss of any label array against a trace,
+ *                                                    without deciding the picture again), fcu_cu_index
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -559,6 +563,68 @@ int  fcu_label_count(const fcu_ctx *c);
  * One kernel on `hip_stream`, asynchronous.  FCU_ERR_ARG: n_pics < 1, a NULL dev_depth or dev_labels. */
 int  fcu_labels_from_rasters(fcu_ctx *c, int n_pics, const uint8_t *dev_depth, const int8_t *dev_part_size, int8_t *dev_labels, void *hip_stream);
 
+/* ---- CU trace: both RD costs of every CU the search visits.  The label maps of fcu_decision_maps cover the CUs on the chosen tree;
+ * the fork's Training dump (tools_YS.cpp:304-318) also holds the CUs its search visited and discarded, and the two costs its
+ * FPLoss / FNLoss are made of: J0, the best cost of the CU coded whole, and J1, the cost of the CU split (TEncCu.cpp:1450-1451; at
+ * depth 3 the cost of SIZE_NxN, :1175-1183).  Optional side output of the ordinary decision, like fcu_pu_trace: bind a device array of
+ * fcu_num_ctus() * FCU_CUS_PER_CTU records to a chain and every CU closed from then on is recorded at [ctu][fcu_cu_index], in every
+ * decision state.  The decisions themselves do not change.
+ *   valid        1 for a CU that lies wholly inside the picture and was visited.  A CU the picture edge cuts is never recorded, nor
+ *                is a CU below a parent that was not divided (Testing state: TerminateCU).
+ *   whole_tried  1 when the whole-CU best cost is a real cost (0: Skip2Nx2N pruned the check; j0 is then FCU_MAX_DOUBLE)
+ *   j0           that cost including the split flag (FCU_MAX_DOUBLE when whole_tried is 0)
+ *   split_tried  depth < 3: the four sub-CUs were searched; depth 3: SIZE_NxN was tried
+ *   j1           the cost of the split / of NxN; 0.0 when split_tried is 0
+ *   split_won    the split (NxN) won: the fork's bPartition_True; 0 when split_tried is 0
+ * A chain with a trace bound clears the 85 records of a CTU when it starts that CTU: the caller clears nothing, and a picture
+ * decided twice into the same array gives the same bytes.  The slice, row and tile chains of a picture are given the same array
+ * and write disjoint CTUs.  fcu_chain_begin and the picture binders start a chain without a trace; NULL stops recording; only the
+ * pointer is copied to the device: position, coder state, counters, search state and labels stay.  FCU_ERR_ARG: a bad chain
+ * index; FCU_ERR_STATE: a chain that is not bound. */
+#define FCU_CUS_PER_CTU 85            /* 1 + 4 + 16 + 64 CUs of depth 0..3 */
+#define FCU_MAX_DOUBLE 1.7e+308       /* HM's MAX_DOUBLE (TypeDef.h): the cost of a CU that was not evaluated */
+typedef struct fcu_cu_trace {         /* 24 B, no implicit padding */
+  double  j0, j1;
+  uint8_t valid, split_won, whole_tried, split_tried, pad[4];
+} fcu_cu_trace;
+/* = fcu_pu_index(depth, 0, zidx): layer offsets 0 / 1 / 5 / 21, inside a layer the CUs in z-order */
+int  fcu_cu_index(int depth, int zidx);
+int  fcu_chain_set_cu_trace(fcu_ctx *c, int chain, fcu_cu_trace *dev_trace);
+
+/* ---- label score: the Verifying counters (g_iVerResult) of ANY label array against the trace of an exhaustively decided picture,
+ * without deciding the picture again.  Every record with valid and split_tried set is a sample: its label is read from the picture's
+ * label array (int8 [NL], the layout of the label maps, the addressing of fcu_chain_set_labels: off(d) + (y / s) * BW(d) + x / s at
+ * picture coordinates) and counted as countTFPN + countRDLoss count it (tools_YS.cpp:968-986): FCU_LABEL_SPLIT predicts 1,
+ * FCU_LABEL_NOT_SPLIT 0, the truth is split_won, fabs(j0 - j1) is added to FPLoss / FNLoss of a wrong prediction.  Any other label
+ * value is no prediction: counted in open[d] and nowhere else.  scored[d] = samples of depth d that had a prediction.
+ * v holds the six counters per depth in the order of fcu_verify_counts: &score.v goes straight into fcu_decision_switch.
+ * Two kernels, no atomics, nothing to clear.  One wave per CTU forms the fcu_ctu_score: counts from ballots, n[d] = TP, FP, TN, FN;
+ * loss[d] = FPLoss, FNLoss, each the sum over the CUs of depth d IN Z-ORDER, one term after the other from 0.0 (a CU that adds
+ * nothing to a sum adds nothing, not 0.0).  One lane per (picture, depth, counter) then adds the CTU records IN RASTER ORDER from
+ * 0.0.  The order is part of the interface (double sums do not commute).  Against the engine's own Verifying counters of the same
+ * labels: the counts are equal; the losses are bit for bit equal when every chain is one CTU, else equal to 1e-9 relative.
+ * (A P picture has depth-3 CUs whose SIZE_NxN is never tried; the Verifying state counts them with J1 = 0 as the fork does, the
+ * score does not -- split_tried is 0 -- so there it is short of the Verifying counters at depth 3 by exactly those CUs.)
+ * dev_trace / dev_labels: host arrays of n_pics device pointers; host_scores receives n_pics records; dev_ctu (device,
+ * [n_pics][fcu_num_ctus], or NULL: a buffer of the context) the per-CTU records.  The call returns after the kernels have finished;
+ * kernel_ms2 (may be NULL) receives their durations.  FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1, a NULL
+ * array, a NULL entry of one, NULL host_scores.  Neither structure has implicit padding.  No CPU fallback. */
+typedef struct fcu_ctu_score { uint16_t n[4][4], open[4], pad[12]; double loss[4][2]; } fcu_ctu_score;   /* 128 B */
+typedef struct fcu_pic_score { fcu_verify_counts v; uint32_t open[4], scored[4]; } fcu_pic_score;       /* 224 B */
+int  fcu_label_score(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace, const int8_t *const *dev_labels,
+                     fcu_pic_score *host_scores, fcu_ctu_score *dev_ctu, float *kernel_ms2, void *hip_stream);
+
+/* ---- trace maps: the trace as the fork's whole Training set, in the layout of the label and N_OBF maps of fcu_decision_maps.
+ * dev_labels int8 [n_pics][NL], dev_j0 / dev_j1 double [n_pics][NL]; each may be NULL, at least one is wanted.  Block (by, bx) of
+ * level d: FCU_LABEL_FORCED for d < 3 and a block not wholly inside the picture; FCU_LABEL_ABSENT for a block whose record has valid 0
+ * or split_tried 0; else split_won.  j0 / j1: the record's costs, 0.0 where the label is ABSENT or FORCED.  Element for element
+ * aligned with the N_OBF map: (feature, label, J0, J1) of every visited CU, with no host pass.  One kernel; every output element is
+ * written by exactly one thread, nothing to clear.  dev_labels may start at any byte, dev_j0 / dev_j1 at multiples of 8.  The call
+ * returns after the kernel has finished; kernel_ms (may be NULL) receives its duration.  FCU_ERR_ARG, argument named: n_pics < 1, a
+ * NULL dev_trace or entry of it, no output wanted, a misaligned cost array. */
+int  fcu_trace_maps(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace,
+                    int8_t *dev_labels, double *dev_j0, double *dev_j1, float *kernel_ms, void *hip_stream);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -594,7 +660,8 @@ const char *fcu_build_info(void);
  * in another language (ctypes, cgo, JNI) checks its own layouts against them before the first call; tests/test_cabi.py does. */
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
        FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9,
-       FCU_ABI_PIC_HASH = 10, FCU_ABI_CTU_MATCH = 11, FCU_ABI_PIC_MATCH = 12 };
+       FCU_ABI_PIC_HASH = 10, FCU_ABI_CTU_MATCH = 11, FCU_ABI_PIC_MATCH = 12, FCU_ABI_CU_TRACE = 13, FCU_ABI_CTU_SCORE = 14,
+       FCU_ABI_PIC_SCORE = 15 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus

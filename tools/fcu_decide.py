@@ -28,6 +28,10 @@ device (fcu_picture_hash): with --report --hash and no --rec no plane is copied 
 64x64 .. 8x8 block ([pictures, ceil(height / s), ceil(width / s)]; -1 absent, 0 not split, 1 split, 2 split forced by the picture edge).
 With --fast it also holds `n_obf0` .. `n_obf3`, the fork's N_OBF feature of the same blocks, for the pictures decided with an OBF map
 (Verifying and Testing), and `n_obf_poc`, the POCs of those pictures.
+--cu-trace FILE.npz decides the Training pictures (all pictures without --fast) with a CU trace bound and saves what fcu_trace_maps
+makes of it on the device: `trace_label`, `j0` and `j1` as arrays [Training pictures, NL] in the flat layout of the label maps (the
+four levels one after the other) -- the split outcome and both RD costs of every CU the exhaustive search visited, not only of those
+on the chosen tree -- and `trace_poc`, the POCs of those pictures.
 """
 import argparse
 import os
@@ -66,6 +70,7 @@ def main():
     ap.add_argument("--rec")
     ap.add_argument("--depth")
     ap.add_argument("--maps", metavar="FILE.npz", help="save the raster depth, part-size, prediction-mode and luma-mode maps and the split-label maps of every picture (with --fast: the N_OBF maps as well)")
+    ap.add_argument("--cu-trace", metavar="FILE.npz", help="decide the Training pictures with a CU trace and save its label / J0 / J1 maps (every CU the search visited)")
     args = ap.parse_args()
     tiles = None
     if args.tiles is not None:
@@ -79,14 +84,14 @@ def main():
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
-        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None,
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None, cu_trace=bool(args.cu_trace),
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
     depths = []
-    maps = {}
+    maps, traces = {}, {}
     n = 0
     t_all = time.perf_counter()
     while n < args.frames:
@@ -134,6 +139,12 @@ def main():
                         maps.setdefault("n_obf%d" % d, []).append(m["n_obf"][d].cpu().numpy().astype(np.uint16))
                 if "n_obf" in m:
                     maps.setdefault("n_obf_poc", []).append(np.int32(r["poc"]))
+        with_trace = [r for r in res if "cu_trace" in r]
+        if args.cu_trace and with_trace:                       # one batched call for the Training pictures of the group
+            tm = dec.eng.trace_maps(with_trace, labels=True, costs=True)
+            for k, name in (("labels", "trace_label"), ("j0", "j0"), ("j1", "j1")):
+                traces.setdefault(name, []).extend(tm[k].cpu().numpy())
+            traces.setdefault("trace_poc", []).extend(np.int32(r["poc"]) for r in with_trace)
         print(f"  {len(res)} picture(s) side by side: {dt * 1e3:.1f} ms", flush=True)
         n += len(res)
     dt_all = time.perf_counter() - t_all
@@ -143,6 +154,8 @@ def main():
         np.save(args.depth, np.stack(depths) if depths else np.zeros((0, 0, 256), np.uint8))
     if args.maps:
         np.savez(args.maps, **{k: np.stack(v) for k, v in maps.items()})
+    if args.cu_trace:
+        np.savez(args.cu_trace, **{k: np.stack(v) for k, v in traces.items()})
     dec.close()
     print(f"{n} pictures decided in {dt_all:.2f} s")
 
