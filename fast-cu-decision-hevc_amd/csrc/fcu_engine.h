@@ -63,6 +63,9 @@ template <class T> static inline T fcu_emu_uni(T v, int site, int line)
   return v;
 }
 #define FCU_FOR_LANES for (int lane = fcu_emu_phase_begin(); lane < 64; lane = fcu_emu_phase_next(lane))
+/* a phase whose results stay in the lanes' registers (LaneVar) or go to memory nothing reads before the next FCU_FOR_LANES
+ * phase has ended: the same lane loop here, no barrier on the device */
+#define FCU_FOR_LANES_REG FCU_FOR_LANES
 #define FCU_ATOMIC_ADD(p, v) (*(p) += (v))
 #define FCU_ATOMIC_MAX(p, v) do { if (*(p) < (v)) *(p) = (v); } while (0)
 #define FCU_ATOMIC_OR(p, v) (*(p) |= (v))
@@ -84,6 +87,7 @@ static unsigned long long g_emu_cu_paths[3] = { 0, 0, 0 };
 #define FCU_INLINE __attribute__((always_inline))
 #define FCU_TABLE __device__ static const
 #define FCU_FOR_LANES for (int lane = (int)threadIdx.x, fcu_once_ = 1; fcu_once_; fcu_once_ = 0, __syncthreads())
+#define FCU_FOR_LANES_REG for (int lane = (int)threadIdx.x, fcu_once_ = 1; fcu_once_; fcu_once_ = 0)
 #define FCU_ATOMIC_ADD(p, v) atomicAdd((p), (v))
 #define FCU_ATOMIC_MAX(p, v) atomicMax((p), (v))
 #define FCU_ATOMIC_OR(p, v) atomicOr((p), (v))
@@ -171,6 +175,13 @@ template <class T> __device__ inline T fcu_uni(T v)
 #define FCU_S7_COEFF(E_, v, comp) do { if (g_S.prof_s7 == 1) FCU_STOC(E_, v, (comp) ? 14 : 13); } while (0)   /* inside a 2Nx2N call of section 7 only */
 #define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
+#elif defined(FCU_PROFILE_PIX)   /* pixel-stage variant: slots 1, 2, 8 and 10 keep their sections; the other twelve belong to the pixel stages before / after the quantiser of pu_first_pass_batched and tu_trial, split by block size (FCU_PTOC, slot = FCU_PIX_SLOT(part, log2)) */
+#define FCU_PTIC(v) long long v = clock64()
+#define FCU_PRST(v) (v = clock64())
+#define FCU_PIX_SLOT(part, log2) ((int)((0x0fedcb976543ull >> (4 * ((part) * 3 + ((log2) >= 4 ? 2 : (log2) - 2)))) & 15))   /* part 0 / 1 = first pass before / after, 2 / 3 = tu_trial before / after: 3 4 5, 6 7 9, 11 12 13, 14 15 0 */
+#define FCU_PTOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } while (0)
+#define FCU_TOC(E_, v, idx) do { if (((idx) == 1 || (idx) == 2 || (idx) == 8 || (idx) == 10) && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_COUNT(E_, idx, n) do { } while (0)
 #else
 #define FCU_TOC(E_, v, idx) do { if (threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { (E_).C->prof[idx] += (unsigned long long)(n); } while (0)
@@ -189,6 +200,11 @@ template <class T> __device__ inline T fcu_uni(T v)
 #endif
 #ifndef FCU_MTOC
 #define FCU_MTOC(E_, v, idx) do { } while (0)
+#endif
+#ifndef FCU_PTOC
+#define FCU_PTIC(v) do { } while (0)
+#define FCU_PRST(v) do { } while (0)
+#define FCU_PTOC(E_, v, idx) do { } while (0)
 #endif
 #ifndef FCU_STOC
 #define FCU_STOC(E_, v, idx) do { } while (0)
@@ -641,17 +657,21 @@ FCU_DEV int coef_remain_bins(uint32_t symbol, uint32_t rparam)             /* by
   return (int)(3 + length + 1 - rparam) + (int)length;
 }
 #ifdef FCU_EMU
-/* test bookkeeping of the emulator (tests/test_walk_prefetch_emu.py, tests/emu/walk_asan_driver.cpp): how often the lane-private
+/* test bookkeeping of the emulator (tests/test_walk_prefetch_emu.py, tests/emu/walk_asan_driver.cpp; SMALL_*:
+ * tests/test_small_tu_emu.py, the edge cases of the 4x4 / 8x8 trials): how often the lane-private
  * walks met their edge cases, and the bounds of the pool rdoq<0> loads from (set by compress_ctu): every address its group loads
  * form is checked against them, because the pools are members of one Scratch block and no sanitizer sees one run into the next */
 enum { WALK_RDOQ_CALLS, WALK_RDOQ_TOP_IS_GROUP0, WALK_RDOQ_AHEAD_GROUPS, WALK_RDOQ_ONLY_GROUP0, WALK_RDOQ_ONLY_LAST_GROUP, WALK_RDOQ_ALL_ZERO,
        WALK_BITS_CALLS, WALK_BITS_ONE_EMPTY_RUN_BETWEEN, WALK_BITS_SECOND_ROUND, WALK_N };
-extern "C" { __attribute__((weak)) unsigned long long fcu_emu_walk_cnt[WALK_N]; }
+enum { SMALL_TS_WINNER, SMALL_ALL_ZERO, SMALL_BATCH_OVER_16, SMALL_CHROMA_4X4, SMALL_N };
+extern "C" { __attribute__((weak)) unsigned long long fcu_emu_walk_cnt[WALK_N]; __attribute__((weak)) unsigned long long fcu_emu_small_cnt[SMALL_N]; }
+#define FCU_SMALL_COUNT(i, n) (fcu_emu_small_cnt[i] += (unsigned long long)(n))
 static const int32_t *g_emu_lscan_lo = nullptr, *g_emu_lscan_hi = nullptr;
 #define FCU_WALK_COUNT(i, n) (fcu_emu_walk_cnt[i] += (unsigned long long)(n))
 #define FCU_CHECK_LSCAN(p) FCU_CHECK((const int32_t *)(p) >= g_emu_lscan_lo && (const int32_t *)(p) < g_emu_lscan_hi)
 #else
 #define FCU_WALK_COUNT(i, n) do { } while (0)
+#define FCU_SMALL_COUNT(i, n) do { } while (0)
 #define FCU_CHECK_LSCAN(p) do { } while (0)
 #endif
 /* TEncSbac::codeCoeffNxN (+codeTransformSkipFlags, codeLastSignificantXY), TEncSbac.cpp:997-1535.
@@ -1286,7 +1306,9 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
 }
 
 /* A value every lane holds one element of, readable and writable by element from wave-uniform code: a register plus
- * v_readlane / v_writelane on the GPU, an array on the CPU emulator (whose lanes run one after the other). */
+ * v_readlane / v_writelane on the GPU, an array on the CPU emulator (whose lanes run one after the other).  from(src), inside a
+ * lane loop, reads the element of another lane, a source index per lane (ds_bpermute on the GPU): the element must have been
+ * set in an earlier lane loop, and on the GPU all 64 lanes must be active at the read. */
 #ifdef FCU_EMU
 template <class T> struct LaneVar {
   T v[64];
@@ -1295,6 +1317,7 @@ template <class T> struct LaneVar {
   T own(int lane) const { return v[lane]; }
   T get(int k) const { return v[k]; }                        /* wave-uniform code: element k */
   void put(int k, T x) { v[k] = x; }
+  T from(int src) const { return v[src & 63]; }              /* inside a lane loop: the element of lane `src`, set in an EARLIER lane loop (a source index per lane) */
 };
 FCU_DEV uint32_t lane_mask16(const LaneVar<int> &f) { uint32_t m = 0; for (int k = 0; k < 16; k++) m |= (uint32_t)(f.v[k] != 0) << k; return m; }
 #else
@@ -1302,10 +1325,12 @@ FCU_DEV uint32_t lane_mask16(const LaneVar<int> &f) { uint32_t m = 0; for (int k
 #define FCU_READLANE(v, k) __builtin_amdgcn_readlane((v), (k))
 #define FCU_WRITELANE(val_, k_, old_) (((int)threadIdx.x == (k_)) ? (val_) : (old_))     /* (this compiler has no v_writelane builtin: compare + select) */
 #define FCU_BALLOT(p) __builtin_amdgcn_ballot_w64(p)
+#define FCU_PERMUTE(v, src) __builtin_amdgcn_ds_bpermute((src) << 2, (v))     /* all 64 lanes active: an inactive source lane reads as 0 */
 #else                                                         /* host pass over the device code: parsed, never run */
 #define FCU_READLANE(v, k) (v)
 #define FCU_WRITELANE(val_, k_, old_) (val_)
 #define FCU_BALLOT(p) ((unsigned long long)(p))
+#define FCU_PERMUTE(v, src) (v)
 #endif
 template <class T> struct LaneVar;
 template <> struct LaneVar<int> {
@@ -1314,6 +1339,7 @@ template <> struct LaneVar<int> {
   __device__ int own(int) const { return r; }
   __device__ int get(int k) const { return FCU_READLANE(r, k); }
   __device__ void put(int k, int x) { r = FCU_WRITELANE(x, k, r); }
+  __device__ int from(int src) const { return FCU_PERMUTE(r, src); }
 };
 template <> struct LaneVar<double> {
   double r = 0;
@@ -1787,6 +1813,38 @@ template <int LOG2> FCU_DEV int32_t fwd2(RowCache<(1 << LOG2), int32_t> &rc, con
 template <int LOG2> FCU_DEV int32_t inv1(RowCache<(1 << LOG2), int32_t> &rc, const int32_t *deqT, int useDst, int idx)
 { constexpr int N = 1 << LOG2; const int y = idx >> LOG2, kh = idx & (N - 1); return clip3i(-32768, 32767, (dot_regs<N>(basis_col<LOG2>(useDst, y), rc.get(deqT + (kh << LOG2))) + 64) >> 7); }
 /* (inv2's input line follows the high index bits: neighbouring lanes share it, one broadcast read per iteration) */
+/* The four passes for a 4x4 or 8x8 block whose samples sit one per lane (lane blk + p holds element p of the block; a wave
+ * holds four 4x4 blocks or one 8x8 block): the input line of a dot product is fetched from the N lanes that hold it instead of
+ * from a pool in scratch.  The same products as above, summed in int32 (the order of the terms cannot matter), so the results
+ * are the pool path's bit for bit.  Called with all 64 lanes active; -DFCU_SMALL_TU_POOLS builds the engine without them. */
+template <int N>
+FCU_DEV int32_t dot_lanes(const int8_t *m, const LaneVar<int> &a, int src0, int step)
+{
+  m = (const int8_t *)__builtin_assume_aligned(m, N);
+  uint32_t mw[N / 4];
+  __builtin_memcpy(mw, m, N);
+  int32_t s = 0;
+#pragma unroll
+  for (int n = 0; n < N; n++) s += (int32_t)(int8_t)(mw[n >> 2] >> (8 * (n & 3))) * a.from(src0 + n * step);
+  return s;
+}
+template <int LOG2> FCU_DEV int32_t fwd1_lanes(const LaneVar<int> &resi, int useDst, int blk, int idx)
+{ constexpr int N = 1 << LOG2, s1 = LOG2 - 1; const int k = idx >> LOG2, y = idx & (N - 1); return (dot_lanes<N>(basis_row<LOG2>(useDst, k), resi, blk + (y << LOG2), 1) + (1 << (s1 - 1))) >> s1; }
+template <int LOG2> FCU_DEV int32_t fwd2_lanes(const LaneVar<int> &tmp, int useDst, int blk, int idx)
+{ constexpr int N = 1 << LOG2, s2 = LOG2 + 6; const int k2 = idx >> LOG2, k1 = idx & (N - 1); return (dot_lanes<N>(basis_row<LOG2>(useDst, k2), tmp, blk + (k1 << LOG2), 1) + (1 << (s2 - 1))) >> s2; }
+/* deq: the de-quantised coefficients in raster order (lane blk + kv * N + kh), not transposed: the step does what tr_index does */
+template <int LOG2> FCU_DEV int32_t inv1_lanes(const LaneVar<int> &deq, int useDst, int blk, int idx)
+{ constexpr int N = 1 << LOG2; const int y = idx >> LOG2, kh = idx & (N - 1); return clip3i(-32768, 32767, (dot_lanes<N>(basis_col<LOG2>(useDst, y), deq, blk + kh, N) + 64) >> 7); }
+template <int LOG2> FCU_DEV int32_t inv2_lanes(const LaneVar<int> &tmp2, int useDst, int blk, int idx)
+{ constexpr int N = 1 << LOG2; const int y = idx >> LOG2, x = idx & (N - 1); return clip3i(-32768, 32767, (dot_lanes<N>(basis_col<LOG2>(useDst, x), tmp2, blk + (y << LOG2), 1) + 2048) >> 12); }
+/* -DFCU_SMALL_TU_POOLS: the engine without the register path, every size through the candidate pools (tests/test_small_tu_emu.py).
+ * tu_trial keeps the pool path for every size: its register path was built and measured, gave nothing on top of the first
+ * pass's and grew the kernels' private segment by 240 B per lane (profiles/small_tu_resources.txt). */
+#ifdef FCU_SMALL_TU_POOLS
+#define FCU_SMALL_TU_REGS(log2) 0
+#else
+#define FCU_SMALL_TU_REGS(log2) ((log2) <= 3)
+#endif
 struct DeqParams { int scale, rs, lo, hi; };                /* xDeQuant flat, TComTrQuant.cpp:1242-1352: loop invariants of one TU */
 FCU_DEV DeqParams deq_params(int log2, int qp)
 {
@@ -2152,9 +2210,12 @@ FCU_DEV FCU_NOINLINE void tu_trial(CuObj *cu, uint32_t tu_k, int comp, int cab, 
   const int useDst = comp == 0 && log2 == 2;
   const int qp = comp ? P.qp_c : P.qp;
 
+  const int filt = use_filtered_ref(mode, log2, comp == 0);
+  if (save1load2 != 2) build_ref(comp, px, py, log2, filt);
+  FCU_PTIC(tp_);
+  const int scanType = coef_scan_idx(mode, log2, comp), qbits = rdoq_qbits(log2, qp), qscale = k_quant_scales[qp % 6];
+  const uint16_t *iscan = k_iscan + k_scan_off[scanType * 4 + log2 - 2];
   if (save1load2 != 2) {
-    const int filt = use_filtered_ref(mode, log2, comp == 0);
-    build_ref(comp, px, py, log2, filt);
     FCU_FOR_LANES {
       const uint8_t *r = filt ? g_S.reff : g_S.ref; const int dc = g_S.dc;
       if (lane == 0) g_S.t_last = -1;
@@ -2176,13 +2237,12 @@ FCU_DEV FCU_NOINLINE void tu_trial(CuObj *cu, uint32_t tu_k, int comp, int cab, 
     }
   }
   /* forward transform; the coefficients go to RDOQ as sign * lLevelDouble in scan order */
-  const int scanType = coef_scan_idx(mode, log2, comp), qbits = rdoq_qbits(log2, qp), qscale = k_quant_scales[qp % 6];
-  const uint16_t *iscan = k_iscan + k_scan_off[scanType * 4 + log2 - 2];
   if (useTS) { FCU_FOR_LANES { est_build(cab, lane); for (int i = lane; i < n2; i += 64) { const int sp = iscan[i]; const int32_t ld = level_double((int32_t)G->p_resi[i] << (15 - 8 - log2), qscale, qbits); G->p_lscan[sp] = ld; if (level_nonzero(ld, qbits)) FCU_ATOMIC_MAX(&g_S.t_last, sp); } } }
   else {
     FCU_FOR_LANES { by_log2(log2, [&](auto L) { constexpr int LG = decltype(L)::value; RowCache<(1 << LG), int16_t> rc; for (int i = lane; i < n2; i += 64) G->p_tmp[i] = fwd1<LG>(rc, G->p_resi, useDst, i); }); }
     FCU_FOR_LANES { est_build(cab, lane); by_log2(log2, [&](auto L) { constexpr int LG = decltype(L)::value; RowCache<(1 << LG), int32_t> rc; for (int i = lane; i < n2; i += 64) { const int sp = iscan[i]; const int32_t ld = level_double(fwd2<LG>(rc, G->p_tmp, useDst, i), qscale, qbits); G->p_lscan[sp] = ld; if (level_nonzero(ld, qbits)) FCU_ATOMIC_MAX(&g_S.t_last, sp); } }); }
   }
+  FCU_PTOC(E, tp_, FCU_PIX_SLOT(2, log2));
   {
     FCU_TIC(t8_);
     const int cbfCtx = comp ? (CTX_CBF_CHROMA + tu.tr_depth) : (CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0));
@@ -2201,7 +2261,9 @@ FCU_DEV FCU_NOINLINE void tu_trial(CuObj *cu, uint32_t tu_k, int comp, int cab, 
     }
     FCU_TOC(E, t8_, 8);
   }
+  FCU_PRST(tp_);                                             /* (the quantiser has its own section) */
   const int absSum = g_S.t_abs;
+  FCU_SMALL_COUNT(SMALL_ALL_ZERO, log2 <= 3 && absSum == 0); FCU_SMALL_COUNT(SMALL_CHROMA_4X4, comp != 0 && log2 == 2);
   FCU_FOR_LANES {                                            /* setCbfPartRange + coefficient store */
     const int np = comp ? tu_nparts_c(tu) : tu.nparts;
     for (int i = lane; i < np; i += 64) cu->cbf[comp][part + i] = (uint8_t)((absSum > 0 ? 1 : 0) << tu.tr_depth);
@@ -2230,6 +2292,7 @@ FCU_DEV FCU_NOINLINE void tu_trial(CuObj *cu, uint32_t tu_k, int comp, int cab, 
     FCU_WAVE_ADD(&g_S.sad[35], sse);
   }
   FCU_SERIAL { const uint32_t sse = g_S.sad[35]; g_S.t_dist = comp ? (uint32_t)(P.chroma_weight * (double)sse) : sse; }
+  FCU_PTOC(E, tp_, FCU_PIX_SLOT(3, log2));
   FCU_TOC(E, t11_, 11);
 }
 
@@ -2293,6 +2356,7 @@ FCU_DEV FCU_NOINLINE void recur_luma_qt(CuObj *cu, uint32_t tu_k, int checkFirst
         }
         if (modeId == 0) FCU_FOR_LANES cab_copy(&g_S.cab[CAB_GOON], slot_ptr(E, fullDepth, CI_QT_TRAFO_ROOT), lane);
       }
+      FCU_SMALL_COUNT(SMALL_TS_WINNER, bestModeId == 1);
       FCU_FOR_LANES { for (int i = lane; i < tu.nparts; i += 64) cu->tskip[0][part + i] = (uint8_t)bestModeId; }
       if (bestModeId == 0) {
         load_intra_result_qt(cu, tu_key(tu), 0);
@@ -2657,6 +2721,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
   if (P.ts_fast) checkTS = checkTS && (partSize == SIZE_NxN);
   const int nc = g_S.n_rd, tsv = checkTS ? 2 : 1, tss = tsv - 1, nvc = nc * tsv;   /* v / tsv == v >> tss, v % tsv == v & tss */
   FCU_CHECK(nvc <= MAXVC && nvc * n2 <= POOL && (MAXLC % 2) == 0);
+  FCU_SMALL_COUNT(SMALL_BATCH_OVER_16, log2 == 2 && nvc > 16);
   const int qbits = rdoq_qbits(log2, P.qp), qscale = k_quant_scales[P.qp % 6];
   const int useDst = log2 == 2;
   const uint8_t *org = G->org[d].y + tu.y * 64 + tu.x;
@@ -2664,6 +2729,41 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
   /* ... and rmd() has just built them for this very block, unless the caller came another way (the tag says) */
   const int haveRefs = FCU_UNI(g_S.ref_tag) == ref_key(cu->x + tu.x, cu->y + tu.y, log2);
   if (!haveRefs) { FCU_TIC(tm_); build_ref(0, cu->x + tu.x, cu->y + tu.y, log2, 1); FCU_MTOC(E, tm_, 14); }
+  FCU_PTIC(tp_);
+  /* 4x4 / 8x8: a sample per lane and the stages in registers, four candidates or one per pass of the wave.  Only what a later
+   * stage or another function reads goes to memory: the prediction (the reference samples die in the quantiser), the
+   * level_double values in scan order, the reconstruction. */
+  const int regs = FCU_SMALL_TU_REGS(log2), blk_mask = ~(n2 - 1), l2n2 = 2 * log2;
+  if (regs) {
+    FCU_FOR_LANES_REG { if (lane == 0) g_S.ref_tag = -1; if (lane < nvc) g_S.vc_last[lane] = -1; }   /* (LDS accesses of one wave stay in program order) */
+    for (int base = 0; base < nc * n2; base += 64) {
+      LaneVar<int> vResi, vT1;
+      FCU_FOR_LANES_REG {                                    /* prediction + residual */
+        const int i = base + lane, act = i < nc * n2, cnd = act ? (i >> l2n2) : 0, p = i & (n2 - 1), y = p >> log2, x = p & (N - 1), mode = g_S.rd_mode[cnd];
+        const uint8_t *r = use_filtered_ref(mode, log2, 1) ? g_S.reff : g_S.ref;
+        const int v = pred_pixel(r, log2, mode, 1, g_S.dc, x, y);
+        int res = 0;
+        if (act) { G->p_pred[i] = (uint8_t)v; res = (int16_t)(org[y * 64 + x] - v); }
+        vResi.set(lane, res);
+      }
+      FCU_FOR_LANES_REG { vT1.set(lane, log2 == 2 ? fwd1_lanes<2>(vResi, useDst, lane & blk_mask, lane & (n2 - 1)) : fwd1_lanes<3>(vResi, 0, lane & blk_mask, lane & (n2 - 1))); }
+      FCU_FOR_LANES_REG {                                    /* second pass + level_double of the candidate's variants: slot v = cand*tsv + ts */
+        const int i = base + lane, act = i < nc * n2, cnd = act ? (i >> l2n2) : 0, p = i & (n2 - 1);
+        const int32_t t = log2 == 2 ? fwd2_lanes<2>(vT1, useDst, lane & blk_mask, p) : fwd2_lanes<3>(vT1, 0, lane & blk_mask, p);
+        if (act) {
+          const uint16_t *iscan = k_iscan + k_scan_off[coef_scan_idx(g_S.rd_mode[cnd], log2, 0) * 4 + log2 - 2];
+          const int sp = iscan[p];
+          for (int ts = 0; ts < tsv; ts++) {
+            const int v = cnd * tsv + ts;
+            const int32_t ld = level_double(ts ? ((int32_t)vResi.own(lane) << (15 - 8 - log2)) : t, qscale, qbits);
+            G->p_lscan[sp * nvc + v] = ld;
+            if (level_nonzero(ld, qbits)) FCU_ATOMIC_MAX(&g_S.vc_last[v], sp);
+          }
+        }
+      }
+    }
+    FCU_FOR_LANES { est_build(CAB_CUR0 + d, lane); }
+  } else {
   FCU_FOR_LANES {                                            /* prediction + residual per candidate */
     if (lane == 0) g_S.ref_tag = -1;                         /* consumed: the quantisation below reuses the arrays */
     const int dc = g_S.dc;
@@ -2688,6 +2788,8 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
       }
     });
   }
+  }
+  FCU_PTOC(E, tp_, FCU_PIX_SLOT(0, log2));
   FCU_TIC(t2_);
   FCU_FOR_LANES {                                            /* RDOQ: one virtual candidate per lane */
     if (lane < nvc) {
@@ -2702,6 +2804,42 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
     if (lane == 0) E.C->n_tu_trials += (unsigned long long)nvc;
   }
   FCU_TOC(E, t2_, 2);
+  FCU_PRST(tp_);
+  if (regs) {
+    const DeqParams dq = deq_params(log2, P.qp);
+    for (int base = 0; base < nvc * n2; base += 64) {        /* four 4x4 variants or one 8x8 variant per pass */
+      const int skip = n2 == 64 && FCU_UNI(g_S.vc_abs[base >> 6]) == 0;   /* an 8x8 variant without levels: its residual is 0 */
+      LaneVar<int> vDeq, vT2, vPO;
+      FCU_FOR_LANES_REG {                                    /* level in raster order + dequantisation; prediction and source sample in the same trip */
+        const int i = base + lane, act = i < nvc * n2, v = act ? (i >> l2n2) : 0, p = i & (n2 - 1), cnd = (v >> tss);
+        int dv = 0, po = 0;
+        if (act) {
+          const uint16_t *iscan = k_iscan + k_scan_off[coef_scan_idx(g_S.rd_mode[cnd], log2, 0) * 4 + log2 - 2];
+          const int sp = iscan[p];
+          const int q = (g_S.vc_abs[v] > 0 && (sp >> 4) <= (g_S.vc_last[v] >> 4)) ? G->p_qscan[sp * nvc + v] : 0;
+          dv = dequant1(q, dq);
+          po = G->p_pred[cnd * n2 + p] | (org[(p >> log2) * 64 + (p & (N - 1))] << 8);
+        }
+        vDeq.set(lane, dv); vPO.set(lane, po);
+      }
+      if (!skip) FCU_FOR_LANES_REG { vT2.set(lane, log2 == 2 ? inv1_lanes<2>(vDeq, useDst, lane & blk_mask, lane & (n2 - 1)) : inv1_lanes<3>(vDeq, 0, lane & blk_mask, lane & (n2 - 1))); }
+      FCU_FOR_LANES_REG {                                    /* second inverse pass + reconstruction + SSE */
+        const int i = base + lane, act = i < nvc * n2, v = act ? (i >> l2n2) : 0, p = i & (n2 - 1), ts = (v & tss);
+        const int t = skip ? 0 : (log2 == 2 ? inv2_lanes<2>(vT2, useDst, lane & blk_mask, p) : inv2_lanes<3>(vT2, 0, lane & blk_mask, p));
+        int e = 0;
+        if (act) {
+          int res = 0;
+          if (g_S.vc_abs[v] > 0) { const int s = 15 - 8 - log2; res = ts ? (int16_t)((vDeq.own(lane) + (1 << (s - 1))) >> s) : t; }
+          const int po = vPO.own(lane), r = clip8((po & 255) + res);
+          G->p_rec[i] = (uint8_t)r;
+          e = (po >> 8) - r;
+        }
+        if (n2 == 64) FCU_WAVE_ADD(&g_S.vc_dist[base >> 6], (uint32_t)(e * e));
+        else if (act) FCU_ATOMIC_ADD(&g_S.vc_dist[v], (uint32_t)(e * e));
+      }
+    }
+    FCU_FOR_LANES { }                                        /* p_rec and vc_dist are complete before the bit count reads them */
+  } else {
   FCU_FOR_LANES {                                            /* levels back to raster order + dequantisation */
     const DeqParams dq = deq_params(log2, P.qp);
     for (int i = lane; i < nvc * n2; i += 64) {
@@ -2735,6 +2873,8 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
       }
     });
   }
+  }
+  FCU_PTOC(E, tp_, FCU_PIX_SLOT(1, log2));
   FCU_TIC(t3_);
   /* Bits of (header, subdiv, cbf, coefficients): xGetIntraBitsQT, one variant per lane on MAXLC lane-private coders.
    * More than MAXLC variants (a 4x4 PU with 9-10 candidates x 2) take a second round; it reuses coder slots, but
@@ -2784,6 +2924,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
   FCU_TOC(E, t3_, 3);
   {                                                          /* xSetIntraResultLumaQT + decision snapshot */
     const int bv = g_S.pu_best_vc, ts = (bv & tss), cbf = g_S.vc_abs[bv] > 0;
+    FCU_SMALL_COUNT(SMALL_TS_WINNER, ts); FCU_SMALL_COUNT(SMALL_ALL_ZERO, log2 <= 3 && !cbf);
     Yuv *reco = &G->reco[d][1 - g_S.reco_best_idx[d]];
     FCU_FOR_LANES {
       for (int i = lane; i < n2; i += 64) {
@@ -3108,6 +3249,7 @@ FCU_DEV FCU_NOINLINE void chroma_leaf_trials(CuObj *cu, uint32_t tu_k)
     if (checkTS) { int nb = 0; const int maxp = tu.part + (tu.c_code_all ? 1 : 4); for (int p = tu.part; p < maxp; p++) nb += cu->tskip[0][p]; checkTS = checkTS && (nb > 0); }
   }
   const int tsv = checkTS ? 2 : 1, tss = tsv - 1;                /* v / tsv == v >> tss, v % tsv == v & tss */
+  FCU_SMALL_COUNT(SMALL_CHROMA_4X4, log2 == 2);                 /* (the chroma trials all run here: nobody calls tu_trial with comp != 0) */
   /* Without a transform-skip trial nothing is coded between the two components (the bits are counted on the whole tree
    * afterwards), so Cb and Cr of a mode are priced against the same coder state and are independent of each other: both
    * go through one round, ten variants side by side.  With the trial the coder moves on after Cb's winner
