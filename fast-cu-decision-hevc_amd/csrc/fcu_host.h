@@ -452,6 +452,30 @@ inline int maps_args_check(int n_pics, const fcu_ctu_out *const *dev_out, int n_
   }
   return FCU_OK;
 }
+/* fcu_feature_count / fcu_feature_maps: F of a set mask (FCU_ERR_ARG for a mask that is empty or has other bits), and what the
+ * call refuses, with the argument named; FCU_OK otherwise */
+inline int feature_count(int sets)
+{
+  if (sets == 0 || (sets & ~(FCU_FEATSET_TMV | FCU_FEATSET_SOC))) return FCU_ERR_ARG;
+  return ((sets & FCU_FEATSET_TMV) ? FCU_FEAT_TMV : 0) + ((sets & FCU_FEATSET_SOC) ? FCU_FEAT_SOC : 0);
+}
+inline int features_args_check(int n_pics, int sets, const uint8_t *const *dev_y, const double *host_yc, const void *dev_features, std::string &err)
+{
+  const std::string who = "fcu_feature_maps: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (feature_count(sets) < 0) bad = "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC";
+  else if (!dev_y) bad = "dev_y is null";
+  else if ((sets & FCU_FEATSET_SOC) && !host_yc) bad = "host_yc is null although FCU_FEATSET_SOC is asked for";
+  else if (!(sets & FCU_FEATSET_SOC) && host_yc) bad = "host_yc is given although FCU_FEATSET_SOC is not asked for";
+  else if (!dev_features) bad = "dev_features is null";
+  else if ((uintptr_t)dev_features & 3) bad = "dev_features starts at a multiple of 4 bytes";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  for (int i = 0; i < n_pics; i++) if (!dev_y[i]) { err = who + "dev_y[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  for (int i = 0; host_yc && i < n_pics * 16; i++)           /* (a Yc beyond any coefficient is a threshold nothing reaches; obf_thr must not overflow) */
+    if (!(host_yc[i] >= 0.0 && host_yc[i] <= 1.0e6)) { err = who + "host_yc[" + std::to_string(i / 16) + "][" + std::to_string(i % 16) + "] is negative or not finite"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
 /* fcu_split_match: likewise */
 inline int match_args_check(int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b, const fcu_pic_match *host_matches, std::string &err)
 {

@@ -23,6 +23,7 @@
 #include "fcu_hash.h"
 #include "fcu_maps.h"
 #include "fcu_trace.h"
+#include "fcu_features.h"
 
 using namespace fcu;
 
@@ -596,7 +597,7 @@ int fcu_obf_prepass(fcu_ctx *c, int n_frames, const uint8_t *dev_y, int16_t *dev
         for (int f = t; f < n_frames; f += nt)
           for (int x = 1; x < 16; x++) {
             const double v = tcm_threshold(&hist[((size_t)f * 15 + (x - 1)) * OBF_HB], nblk);
-            yc[(size_t)f * 16 + x] = v; thr[(size_t)f * 16 + x] = (int)(v * 8.0);
+            yc[(size_t)f * 16 + x] = v; thr[(size_t)f * 16 + x] = obf_thr(v);
           }
       });
     for (auto &th : pool) th.join();
@@ -1022,6 +1023,40 @@ int fcu_trace_maps(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace,
   HIPCHK(hipGetLastError());
   HIPCHK(ev.record(1));
   HIPCHK(hipStreamSynchronize(st));                          /* dev_trace (the caller's array) is done with */
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+/* the fork's TMV / SOC features per block of the label maps: feat_ctu (fcu_features.h), one launch for the batch */
+int fcu_feature_count(int sets)
+{
+  const int f = feature_count(sets);
+  return f < 0 ? fail(FCU_ERR_ARG, "fcu_feature_count: sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC") : f;
+}
+int fcu_feature_maps(fcu_ctx *c, int n_pics, int sets, const uint8_t *const *dev_y, const double *host_yc, float *dev_features, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_feature_maps: null context");
+  { std::string err; const int rc = features_args_check(n_pics, sets, dev_y, host_yc, dev_features, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  HIPCHK(c->maps.reserve(up(sizeof(FeatPic) * n_pics), st));
+  FeatPic *d_pics = (FeatPic *)c->maps.p;
+  std::vector<FeatPic> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) {
+    hp[i].y = dev_y[i];
+    for (int k = 0; k < 16; k++) hp[i].thr[k] = host_yc ? obf_thr(host_yc[(size_t)i * 16 + k]) : 0;
+  }
+  HIPCHK(hipMemcpyAsync(d_pics, hp.data(), sizeof(FeatPic) * n_pics, hipMemcpyHostToDevice, st));
+  const dim3 grid(G.n_ctu, n_pics), block(FEAT_THREADS);
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  if (sets == FCU_FEATSET_TMV) hipLaunchKernelGGL((feat_ctu<FCU_FEATSET_TMV>), grid, block, 0, st, d_pics, dev_features, G);
+  else if (sets == FCU_FEATSET_SOC) hipLaunchKernelGGL((feat_ctu<FCU_FEATSET_SOC>), grid, block, 0, st, d_pics, dev_features, G);
+  else hipLaunchKernelGGL((feat_ctu<FCU_FEATSET_TMV | FCU_FEATSET_SOC>), grid, block, 0, st, d_pics, dev_features, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp (the host descriptors) is done with */
   if (kernel_ms) ev.ms(kernel_ms, 0, 1);
   return FCU_OK;
 }

@@ -12,6 +12,8 @@
  *   obf_count  every block again (recomputing the DCT costs less traffic than storing 15 coefficients per block):
  *              OBF = number of AC coefficients with |coef| >= Yc*8 (BINARIZE_OBF 0), one int16 per block
  * Algorithmic bytes per frame: read W*H (hist) + read W*H, write W*H/8 (count).
+ * obf_dct4, obf_thr and obf_outlier are shared with the feature kernel (fcu_features.h), whose CPU build (FCU_EMU) leaves the
+ * kernels of this file out.
  */
 #pragma once
 #include <math.h>
@@ -49,6 +51,14 @@ __device__ static inline void obf_dct4(const uint32_t r[4], int coef[16])
   }
 }
 
+/* Yc of a frequency (a bucket index of |coef / 8|) as the threshold on the coefficient itself (DctScaling 8, :1010) */
+inline int obf_thr(double yc) { return (int)(yc * 8.0); }
+/* the outlier test on a coefficient c, a = |c|: c != 0  <=>  not (c < Yc*8 && c > -Yc*8)  (:1009-1038).  One definition; obf_count
+ * takes it as the expression (its code stays instruction for instruction what it was), the feature kernel as the function */
+#define OBF_OUTLIER(c, a, thr) ((c) != 0 && (a) >= (thr))
+__device__ static inline bool obf_outlier(int c, int thr) { const int a = c < 0 ? -c : c; return OBF_OUTLIER(c, a, thr); }
+
+#ifndef FCU_EMU
 /* A thread owns groups of four horizontally adjacent blocks: four 16-byte row loads (consecutive lanes read
  * consecutive 16 bytes of a picture row), four DCTs.  Width is a multiple of 8 (SPS), so a row holds an even
  * number of blocks; the last group of a row may hold fewer than four. */
@@ -118,8 +128,7 @@ __global__ void __launch_bounds__(OBF_THREADS) obf_hist(const uint8_t *y, int w,
   }
 }
 
-/* thr[frame][16] = Yc * 8 as an integer (Yc is a bucket index); OBF = number of AC coefficients with |c| >= thr,
- * c != 0  <=>  not (c < Yc*8 && c > -Yc*8)  (:1009-1038) */
+/* thr[frame][16] = obf_thr(Yc); OBF = number of AC coefficients that are outliers (obf_outlier) */
 __global__ void __launch_bounds__(OBF_THREADS) obf_count(const uint8_t *y, int w, int h, size_t frame_bytes, const int *thr, int16_t *obf)
 {
   const int bw = w >> 2, gpr = (bw + 3) >> 2, ngrp = gpr * (h >> 2);
@@ -141,7 +150,7 @@ __global__ void __launch_bounds__(OBF_THREADS) obf_count(const uint8_t *y, int w
       obf_dct4(r, coef);
       int n = 0;
 #pragma unroll
-      for (int x = 1; x < 16; x++) { const int c = coef[x], a = c < 0 ? -c : c; n += (c != 0 && a >= t[x]); }
+      for (int x = 1; x < 16; x++) { const int c = coef[x], a = c < 0 ? -c : c; n += OBF_OUTLIER(c, a, t[x]); }
       res[j] = (int16_t)n;
     }
     int16_t *o = out + (size_t)gy * bw + gx * 4;
@@ -149,6 +158,8 @@ __global__ void __launch_bounds__(OBF_THREADS) obf_count(const uint8_t *y, int w
     else { o[0] = res[0]; o[1] = res[1]; }
   }
 }
+
+#endif /* FCU_EMU */
 
 /* ---- host: TCMprocessOneSequence and helpers, TEncSlice.cpp:194-392 ---------------------------------------- */
 struct TcmBucket { int count; double acum_abs_amp, acum_samp_num, prob, lambda, likelyhood; };

@@ -184,7 +184,7 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
            "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices",
            "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters",
-           "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps"]
+           "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps", "fcu_feature_count", "fcu_feature_maps"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -199,6 +199,34 @@ CU_TRACE_DTYPE = np.dtype([("j0", np.float64), ("j1", np.float64), ("valid", np.
                            ("split_tried", np.uint8), ("pad", np.uint8, (4,))])                                                    # fcu_cu_trace
 CTU_SCORE_DTYPE = np.dtype([("n", np.uint16, (4, 4)), ("open", np.uint16, (4,)), ("pad", np.uint16, (12,)), ("loss", np.float64, (4, 2))])   # fcu_ctu_score
 PIC_SCORE_DTYPE = np.dtype([("v", np.float64, (4, 6)), ("open", np.uint32, (4,)), ("scored", np.uint32, (4,))])                    # fcu_pic_score
+
+
+# FCU_FEATSET_*: the feature sets of fcu_feature_maps, in column order, and the names of their columns (include/fcu.h):
+# tmv_<filter>_<mean | var>_<region>, column f * 26 + k, and soc_<k>, k = y * 4 + x of the 4x4 DCT
+FEATURE_SETS = {"tmv": 1, "soc": 2}
+FEATURE_COUNTS = {"tmv": 130, "soc": 16}                  # FCU_FEAT_TMV, FCU_FEAT_SOC
+TMV_FILTERS = ("org", "hor", "ver", "diag", "antd")
+# k = 20 / 24 ("q_bottom") are the fork's third "quadrant": all columns of the bottom rows, equal to k = 3 / 5
+TMV_STATS = ("mean_all", "var_all", "mean_top", "mean_bottom", "var_top", "var_bottom", "mean_left", "mean_right", "var_left", "var_right",
+             "mean_tri_tl", "mean_tri_br", "var_tri_tl", "var_tri_br", "mean_tri_tr", "mean_tri_bl", "var_tri_tr", "var_tri_bl",
+             "mean_q_tl", "mean_q_tr", "mean_q_bottom", "mean_q_br", "var_q_tl", "var_q_tr", "var_q_bottom", "var_q_br")
+FEATURE_NAMES = tuple("tmv_%s_%s" % (f, k) for f in TMV_FILTERS for k in TMV_STATS) + tuple("soc_%d" % k for k in range(16))
+
+
+def feature_sets(sets):
+    """the names of `sets` (one name or several, any order) as (mask, names in column order)"""
+    sets = (sets,) if isinstance(sets, str) else tuple(sets)
+    for n in sets:
+        if n not in FEATURE_SETS:
+            raise ValueError("feature sets are among %s, not %r" % (sorted(FEATURE_SETS), n))
+    names = tuple(n for n in FEATURE_SETS if n in sets)
+    return sum(FEATURE_SETS[n] for n in names), names
+
+
+def feature_columns(sets):
+    """the column names of feature_maps(..., sets=sets), in column order"""
+    _, names = feature_sets(sets)
+    return tuple(c for c in FEATURE_NAMES if c.split("_")[0] in names)
 
 
 def cu_index(depth, zidx):
@@ -300,6 +328,8 @@ def load_lib():
     lib.fcu_chain_set_cu_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.fcu_label_score.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_trace_maps.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_feature_count.argtypes = [C.c_int]
+    lib.fcu_feature_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     _lib = lib
     return lib
 
@@ -787,6 +817,37 @@ class CuEngine:
         self._chk(self.lib.fcu_trace_maps(self.h, n, tp, ptr(d_lab), ptr(d_j0), ptr(d_j1), C.byref(ms) if timed else None, s), "fcu_trace_maps")
         res = {k: v for k, v in (("labels", d_lab), ("j0", d_j0), ("j1", d_j1)) if v is not None}
         return (res, float(ms.value)) if timed else res
+
+    # -- getTMVFeature / FormFeatureVector(SOC)
+    def feature_maps(self, lumas, sets=("tmv", "soc"), yc=None, timed=False, stream=None):
+        """The fork's per-CU model inputs, formed on the device from the luma planes (fcu_feature_maps): the 5 x 26 TMV texture
+        statistics of getTMVFeature ("tmv", 130 columns) and the outlier-coefficient sums of FormFeatureVector ("soc", 16
+        columns); definition and quirks: include/fcu.h.  lumas: list of uint8 device tensors [height, width] (dense; views at
+        any byte offset allowed), or of dicts with `org` or of (Y, U, V) triples, of which the luma plane is read.  yc: float64
+        [n, 16], the thresholds obf_prepass returned for these pictures -- given exactly when "soc" is asked for.
+        Returns a float32 device tensor [n, NL, F] (F = len(feature_columns(sets)), "tmv" columns first): row r of picture i
+        belongs to the block of row r of decision_maps(...)["labels"] / ["n_obf"] flattened and of trace_maps(...); a block
+        the picture edge cuts (LABEL_FORCED) has a row of zeros.  timed=True: (tensor, kernel ms)."""
+        torch = self.torch
+        mask, names = feature_sets(sets)
+        n, NL, F = len(lumas), self.label_count(), sum(FEATURE_COUNTS[k] for k in names)
+        dev = torch.device("cuda", self.device)
+        ptrs, keep = (C.c_void_p * max(n, 1))(), []
+        for i, p in enumerate(lumas):
+            t = p["org"][0] if isinstance(p, dict) else (p if torch.is_tensor(p) else p[0])
+            assert t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (self.height, self.width) and t.is_contiguous(), "feature_maps: dense uint8 luma planes on the device"
+            keep.append(t)
+            ptrs[i] = t.data_ptr()
+        ycp = None
+        if yc is not None:
+            yc = np.ascontiguousarray(np.asarray(yc, np.float64).reshape(-1, 16))
+            assert yc.shape[0] == n, "feature_maps: one row of 16 thresholds per picture"
+            ycp = yc.ctypes.data
+        out = torch.empty((n, NL, F), dtype=torch.float32, device=dev)
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_feature_maps(self.h, n, mask, ptrs, ycp, out.data_ptr(), C.byref(ms) if timed else None, s), "fcu_feature_maps")
+        return (out, float(ms.value)) if timed else out
 
     # -- TComLoopFilter::loopFilterPic
     def deblock(self, chain=None, beta_offset_div2=0, tc_offset_div2=0, timed=False, stream=None, out=None, rec=None, tiles=None, lf_cross_tiles=1, slice_ctus=None, lf_cross_slices=1, layout=None):

@@ -96,7 +96,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, cu_trace=False, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, cu_trace=False, features=None, **flags):
         """cu_trace=True: every Training picture (all of them with fast=False) is decided with a CU trace bound to its chains
         (CuEngine.enable_cu_trace): its result dict gains `cu_trace`, the device tensor of n_ctu x 85 fcu_cu_trace records -- J0, J1 and
         the outcome of every CU the exhaustive search visited; CuEngine.trace_maps and CuEngine.label_score take it as it is.
@@ -130,8 +130,14 @@ class SequenceDecider:
         maps=True, or a dict of CuEngine.decision_maps' keyword arguments (fields, mv, labels): every result dict gains `maps`, the
         picture's raster maps as device tensors -- by default the depth, part-size, prediction-mode and luma-mode maps and the four
         split-label maps; a picture that was decided with an OBF map (fast=True, outside Training) also gets `n_obf`.  They are
-        formed after the launch, one batched call per group."""
+        formed after the launch, one batched call per group.
+        features=True, or a tuple of feature-set names ("tmv", "soc"; True means both): every result dict gains `features`, the
+        float32 device tensor [NL, F] of CuEngine.feature_maps -- the fork's TMV / SOC model inputs of every block, row for row
+        aligned with the label / N_OBF maps and with CuEngine.trace_maps of `cu_trace` -- formed in one batched call per group from
+        the source planes the chains were bound with.  With "soc" the OBF pre-pass runs for Training pictures too (it already runs
+        for the others) to get the picture's thresholds; a Training chain is not given the map, so no decision changes."""
         self.do_report = report
+        self.features = None if features is None or features is False else _engine.feature_sets(("tmv", "soc") if features is True else features)[1]
         if labels is not None and not callable(labels):
             raise ValueError("SequenceDecider: labels is a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None")
         self.labels = labels
@@ -178,8 +184,10 @@ class SequenceDecider:
             state, sk, te = self.schedule.begin_picture(poc) if self.fast else (TRAINING, np.zeros(4, np.uint8), np.zeros(4, np.uint8))
             first = i * self.n_slices
             n_sl, rec, out = eng.init_picture(first, yuv, self.qp, self.layout, **self.flags)
+            yc = None
             if state != TRAINING:
-                obf = eng.obf_prepass(eng.org_planes(first)[0])[0][0].contiguous()
+                obf, yc, _ = eng.obf_prepass(eng.org_planes(first)[0])
+                obf = obf[0].contiguous()
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
                 lab = self.labels(poc, eng.org_planes(first), obf) if self.labels is not None else None
@@ -195,6 +203,8 @@ class SequenceDecider:
                 pics[-1]["labels"] = lab
             if self.maps and state != TRAINING:
                 pics[-1]["obf"] = obf
+            if self.features and "soc" in self.features:       # the thresholds of the picture's own pre-pass; the map is not bound in Training
+                pics[-1]["yc"] = yc[0] if yc is not None else eng.obf_prepass(eng.org_planes(first)[0])[1][0]
         eng.compress_pictures(0, len(yuvs), self.layout)
         nb = _engine.CTU_OUT_BYTES
         for p in pics:
@@ -213,6 +223,11 @@ class SequenceDecider:
             obf = [p.pop("obf") for p in pics] if "obf" in pics[0] else None
             for p, m in zip(pics, split_batch_maps(eng.decision_maps(pics, obf=obf, **self.maps), len(pics))):
                 p["maps"] = m
+        if self.features:
+            yc = np.stack([p.pop("yc") for p in pics]) if "soc" in self.features else None
+            feat = eng.feature_maps([eng.org_planes(p["first"])[0] for p in pics], sets=self.features, yc=yc)
+            for i, p in enumerate(pics):
+                p["features"] = feat[i]
         eng.sync()
         for p in pics:
             p["depth"] = p["out"].view(eng.n_ctu, nb)[:, :256].cpu().numpy().copy()      # fcu_ctu_out.depth leads the struct

@@ -625,6 +625,62 @@ int  fcu_label_score(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trac
 int  fcu_trace_maps(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace,
                     int8_t *dev_labels, double *dev_j0, double *dev_j1, float *kernel_ms, void *hip_stream);
 
+/* ---- feature maps: the inputs of a partition model, per block of the label / N_OBF maps above and row for row aligned with them:
+ * (X, label, J0, J1) of a Training picture are device arrays with no host pass.  The fork dumps these next to every Training label
+ * (TEncCu.cpp:1558-1579).  dev_features is float32 [n_pics][NL][F]: block (by, bx) of level d (s = 64 >> d, luma (bx s, by s)) is row
+ * off(d) + by BW(d) + bx; a block that does not lie wholly inside the picture gets a row of zeros (the fork forms features only
+ * under !bBoundary, TEncCu.cpp:1525).  The columns of FCU_FEATSET_TMV come first, then those of FCU_FEATSET_SOC.
+ *
+ * TMV, column f * 26 + k: getTMVFeature (tools_YS.cpp:1682-1839).  For the W x W samples p[i][j] of the block (W = s, i = row,
+ * j = column) filter f gives a W x W plane q that is ZERO on its one-sample border ring -- the ring of this CU, not of the picture,
+ * and the identity filter has it too (T3x3Filter::filter, :1659-1672) -- and, for 1 <= i, j <= W - 2,
+ *   f = 0  p[i][j]                    f = 1  p[i][j-1] - p[i][j+1]          f = 2  p[i-1][j] - p[i+1][j]
+ *   f = 3  p[i-1][j+1] - p[i+1][j-1]  f = 4  p[i-1][j-1] - p[i+1][j+1]      (masks :1693-1697)
+ * so a block's features depend on its own samples only.  A rectangle R of N elements with sum S has mean = S / N and "variance" =
+ * (sum over R of |trunc(q - mean)|) / N, truncation toward zero (getSubBlockMean / getSubBlockVariance, tools_YS.h:106-126).  The
+ * four triangles hold W (W + 1) / 2 elements each but divide by W W / 2, and their "variance" loop ASSIGNS instead of adding
+ * (`iVariance =`, :1749-1811): it is |trunc(q_last - mean)| / (W W / 2) for the last element of the loop, which always lies on the
+ * zero ring, i.e. floor(|mean|) / (W W / 2).
+ *   k = 0 / 1           mean / variance of the whole block
+ *   k = 2, 3 / 4, 5     means / variances of rows [0, W/2) and rows [W/2, W)
+ *   k = 6, 7 / 8, 9     ... of columns [0, W/2) and columns [W/2, W)
+ *   k = 10, 11 / 12, 13 ... of the triangles j < W - i and j >= W - i - 1
+ *   k = 14, 15 / 16, 17 ... of the triangles j >= i and j <= i
+ *   k = 18, 19, 20, 21 / 22, 23, 24, 25   ... of the top-left quadrant, the top-right quadrant, THE BOTTOM HALF (rows [W/2, W), all
+ *                       columns: the fork passes (0, uiCuWidth) as the column range of its third "quadrant", :1823-1825, so k = 20 /
+ *                       24 repeat k = 3 / 5) and the bottom-right quadrant.
+ * Every divisor is a power of two and |S| <= 4096 * 255, so every value is an integer below 2^24 times a power of two: float32
+ * holds the fork's doubles exactly, and the kernel is integer-only, |trunc(q - S/N)| = |q N - S| >> log2 N.  No floating-point
+ * ordering enters the interface.
+ *
+ * SOC, column k = y * 4 + x (after the TMV columns when both sets are asked for): FormFeatureVector, Type SOC
+ * (tools_YS.cpp:379-396), on the Outlier plane of getOutlierWithDCT (TEncSlice.cpp:1057-1132) with REVERSETRANSFORM_OUTLIER 0 and
+ * BINARIZE_OUTLIER 0 (TypeDef.h:126-127): the plane holds |coef| / 100 (integer division) at the coefficient's position in its 4x4
+ * block, for the coefficients the pre-pass keeps as outliers and 0 for the others.  SOC[k] = sum over the 4x4 blocks of the CU of
+ * |coef[k]| / 100 where coefficient k (frequency k of fcu_obf_prepass, k = 1..15) is an outlier: coef != 0 and |coef| >= (int)(Yc[k] * 8),
+ * the test and the threshold of fcu_obf_prepass, one function for both.  SOC[0] (DC) is 0.  host_yc: double [n_pics][16], the Yc
+ * fcu_obf_prepass returned for each picture (entry 0 is not read).  Sums stay below 2^24: exact in float32.
+ * The fork's SUBSOC of a depth-d CU (:397-444) is the SOC of its four sub-blocks: the rows of the blocks
+ * (2 by, 2 bx), (2 by, 2 bx + 1), (2 by + 1, 2 bx), (2 by + 1, 2 bx + 1) of level d + 1, in that order; it is not emitted a second
+ * time (and SOC of level d is the sum of those four rows).
+ * Out of scope: the OBF / EOBF patches and Outlier / BOutlier are crops of maps the caller can already form (fcu_obf_prepass, the
+ * luma plane); OBF_SATD* carries only the patch -- its SATD / RDCost lines are commented out in the fork; the models themselves.
+ *
+ * dev_y: host array of n_pics device pointers to dense width x height luma planes, each may start at any byte (a plane on an
+ * 8-byte boundary is read with 8-byte loads).  dev_features: 4-byte aligned.  One kernel on `hip_stream`, one workgroup per CTU; every
+ * output element, the zero rows included, is written by exactly one thread, no atomics, nothing to clear: the same input gives
+ * the same bytes.  The call returns after the kernel has finished; kernel_ms (may be NULL) receives its duration.
+ * FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1; sets 0 or with other bits; a NULL dev_y or entry of it;
+ * FCU_FEATSET_SOC without host_yc and host_yc without it; a negative or non-finite Yc; a NULL or misaligned dev_features.
+ * No CPU fallback. */
+enum { FCU_FEATSET_TMV = 1, FCU_FEATSET_SOC = 2 };
+#define FCU_FEAT_TMV 130
+#define FCU_FEAT_SOC 16
+/* F of a set mask: 130, 16 or 146; FCU_ERR_ARG for any other mask */
+int  fcu_feature_count(int sets);
+int  fcu_feature_maps(fcu_ctx *c, int n_pics, int sets, const uint8_t *const *dev_y, const double *host_yc,
+                      float *dev_features, float *kernel_ms, void *hip_stream);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the

@@ -32,6 +32,9 @@ With --fast it also holds `n_obf0` .. `n_obf3`, the fork's N_OBF feature of the 
 makes of it on the device: `trace_label`, `j0` and `j1` as arrays [Training pictures, NL] in the flat layout of the label maps (the
 four levels one after the other) -- the split outcome and both RD costs of every CU the exhaustive search visited, not only of those
 on the chosen tree -- and `trace_poc`, the POCs of those pictures.
+--features FILE.npz saves the fork's TMV and SOC model inputs of every block, formed on the device (fcu_feature_maps): `features`
+[pictures, NL, 146] float32, `feature_names` (the 146 column names) and `features_poc`.  Row r of a picture is the block of element r
+of `trace_label` / `j0` / `j1` of --cu-trace for the picture of the same POC: the arrays line up row for row.
 """
 import argparse
 import os
@@ -71,6 +74,8 @@ def main():
     ap.add_argument("--depth")
     ap.add_argument("--maps", metavar="FILE.npz", help="save the raster depth, part-size, prediction-mode and luma-mode maps and the split-label maps of every picture (with --fast: the N_OBF maps as well)")
     ap.add_argument("--cu-trace", metavar="FILE.npz", help="decide the Training pictures with a CU trace and save its label / J0 / J1 maps (every CU the search visited)")
+    ap.add_argument("--features", metavar="FILE.npz", help="save the TMV + SOC features of every block of every picture (features [pictures, NL, 146], feature_names, features_poc); "
+                                                           "with --cu-trace the arrays line up row for row: row r of `features` of a picture is the block of element r of trace_label / j0 / j1 of the same POC")
     args = ap.parse_args()
     tiles = None
     if args.tiles is not None:
@@ -84,14 +89,14 @@ def main():
     seq = pkg.sequence
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
-        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None, cu_trace=bool(args.cu_trace),
+        dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None, cu_trace=bool(args.cu_trace), features=True if args.features else None,
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
     names = {seq.TRAINING: "training", seq.VERIFYING: "verifying", seq.TESTING: "testing"}
     rec_f = open(args.rec, "wb") if args.rec else None
     depths = []
-    maps, traces = {}, {}
+    maps, traces, feats = {}, {}, {}
     n = 0
     t_all = time.perf_counter()
     while n < args.frames:
@@ -139,6 +144,9 @@ def main():
                         maps.setdefault("n_obf%d" % d, []).append(m["n_obf"][d].cpu().numpy().astype(np.uint16))
                 if "n_obf" in m:
                     maps.setdefault("n_obf_poc", []).append(np.int32(r["poc"]))
+            if args.features:
+                feats.setdefault("features", []).append(r["features"].cpu().numpy())
+                feats.setdefault("features_poc", []).append(np.int32(r["poc"]))
         with_trace = [r for r in res if "cu_trace" in r]
         if args.cu_trace and with_trace:                       # one batched call for the Training pictures of the group
             tm = dec.eng.trace_maps(with_trace, labels=True, costs=True)
@@ -156,6 +164,8 @@ def main():
         np.savez(args.maps, **{k: np.stack(v) for k, v in maps.items()})
     if args.cu_trace:
         np.savez(args.cu_trace, **{k: np.stack(v) for k, v in traces.items()})
+    if args.features:
+        np.savez(args.features, feature_names=np.array(pkg.engine.FEATURE_NAMES), **{k: np.stack(v) for k, v in feats.items()})
     dec.close()
     print(f"{n} pictures decided in {dt_all:.2f} s")
 
