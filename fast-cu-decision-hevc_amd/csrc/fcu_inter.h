@@ -923,6 +923,7 @@ FCU_DEV FCU_NOINLINE void inter_tu_trials(CuObj *cu, uint32_t tu_k, int addZero)
     const int comp = v >> 1;
     if (!(comp ? waveC : waveY) || comp >= ncomp) continue;
     const int cbfCtx = (comp == 0 && trMode == 0) ? EST_ROOT_CBF : qt_cbf_ctx(tu, comp);      /* blockRootCbpBits, TComTrQuant.cpp:2358 */
+    FCU_TAIL_COUNT(TAIL_INTER, 1);
     rdoq_wave(CAB_GOON, G->p_lscan + voff(v), G->p_qscan + voff(v), FCU_UNI(g_S.iv_top[v]), bl2[comp], comp ? 1 : 0, 0, cbfCtx, P, G->r_rec + voff(v), G->r_cg + v * 64);
     FCU_SERIAL { g_S.iv_abs[v] = g_S.rw_abs; g_S.iv_lsp[v] = g_S.rw_lsp; }
   }
