@@ -476,6 +476,80 @@ inline int features_args_check(int n_pics, int sets, const uint8_t *const *dev_y
     if (!(host_yc[i] >= 0.0 && host_yc[i] <= 1.0e6)) { err = who + "host_yc[" + std::to_string(i / 16) + "][" + std::to_string(i % 16) + "] is negative or not finite"; return FCU_ERR_ARG; }
   return FCU_OK;
 }
+/* ---- the risk-table model (include/fcu.h).  risk_q and risk_rule are the one definition of the quantised loss and of the decision
+ * rule: the kernels of fcu_risk.h call them on the device, fcu_risk_table below on the host */
+#if defined(__HIPCC__) && !defined(FCU_EMU)
+#define FCU_HOST_DEV __host__ __device__
+#else
+#define FCU_HOST_DEV
+#endif
+/* (int64) floor(fabs(j0 - j1) * 256), clamped to 2^40 - 1; whatever is not < 2^40 -- NaN, infinity -- gives 2^40 - 1 */
+FCU_HOST_DEV inline int64_t risk_q(double j0, double j1)
+{
+  const double s = fabs(j0 - j1) * 256.0;                    /* (exact: a power of two) */
+  return s < 1099511627776.0 ? (int64_t)floor(s) : FCU_RISK_Q_MAX;
+}
+/* the fork's R0 < R1 -> TerminateCU, else Skip2Nx2N: r0 = risk[..][0] (the loss of predicting SPLIT), r1 = risk[..][1] */
+FCU_HOST_DEV inline int risk_rule(int64_t r0, int64_t r1, uint32_t c0, uint32_t c1, int min_count)
+{
+  if ((uint64_t)c0 + c1 < (uint64_t)min_count) return FCU_LABEL_ABSENT;
+  return r1 < r0 ? FCU_LABEL_NOT_SPLIT : FCU_LABEL_SPLIT;
+}
+/* fcu_risk_table */
+inline void risk_table(const fcu_risk_model *m, int min_count, int8_t table[4][FCU_RISK_BINS])
+{
+  for (int d = 0; d < 4; d++) for (int x = 0; x < FCU_RISK_BINS; x++)
+    table[d][x] = (int8_t)risk_rule(m->risk[d][x][0], m->risk[d][x][1], m->count[d][x][0], m->count[d][x][1], min_count);
+}
+/* what the three calls refuse, with the argument named; FCU_OK otherwise.  n_blocks = NL of the context's picture size */
+inline int risk_null_entry(const std::string &who, const char *name, const void *const *a, int n_pics, std::string &err)
+{
+  for (int i = 0; i < n_pics; i++) if (!a[i]) { err = who + name + "[" + std::to_string(i) + "] is null"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int risk_train_args_check(int n_pics, const fcu_cu_trace *const *dev_trace, const uint16_t *const *dev_keys, const void *dev_model, int accumulate, int n_blocks, std::string &err)
+{
+  const std::string who = "fcu_risk_train: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_trace) bad = "dev_trace is null";
+  else if (!dev_keys) bad = "dev_keys is null";
+  else if (!dev_model) bad = "dev_model is null";
+  else if ((uintptr_t)dev_model & 7) bad = "dev_model starts at a multiple of 8 bytes";
+  else if (accumulate != 0 && accumulate != 1) bad = "accumulate is 0 or 1";
+  else if ((int64_t)n_pics * n_blocks > FCU_RISK_MAX_BLOCKS) bad = "n_pics * NL is at most 2^22 in one call";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  if (risk_null_entry(who, "dev_trace", (const void *const *)dev_trace, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  if (risk_null_entry(who, "dev_keys", (const void *const *)dev_keys, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  for (int i = 0; i < n_pics; i++) if ((uintptr_t)dev_keys[i] & 1) { err = who + "dev_keys[" + std::to_string(i) + "] starts at an even byte"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int risk_predict_args_check(int n_pics, const uint16_t *const *dev_keys, const void *dev_model, int min_count, const void *dev_labels, std::string &err)
+{
+  const std::string who = "fcu_risk_predict: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_keys) bad = "dev_keys is null";
+  else if (!dev_model) bad = "dev_model is null";
+  else if ((uintptr_t)dev_model & 7) bad = "dev_model starts at a multiple of 8 bytes";
+  else if (min_count < 0) bad = "min_count must not be negative";
+  else if (!dev_labels) bad = "dev_labels is null";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  if (risk_null_entry(who, "dev_keys", (const void *const *)dev_keys, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  for (int i = 0; i < n_pics; i++) if ((uintptr_t)dev_keys[i] & 1) { err = who + "dev_keys[" + std::to_string(i) + "] starts at an even byte"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int nobf_args_check(int n_pics, const int16_t *const *dev_obf, const void *dev_nobf, std::string &err)
+{
+  const std::string who = "fcu_nobf_maps: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (!dev_obf) bad = "dev_obf is null";
+  else if (!dev_nobf) bad = "dev_nobf is null";
+  else if ((uintptr_t)dev_nobf & 1) bad = "dev_nobf starts at an even byte";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  return risk_null_entry(who, "dev_obf", (const void *const *)dev_obf, n_pics, err);
+}
 /* fcu_split_match: likewise */
 inline int match_args_check(int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b, const fcu_pic_match *host_matches, std::string &err)
 {

@@ -24,6 +24,7 @@
 #include "fcu_maps.h"
 #include "fcu_trace.h"
 #include "fcu_features.h"
+#include "fcu_risk.h"
 
 using namespace fcu;
 
@@ -122,6 +123,7 @@ struct fcu_ctx {
   DevBuf rep;                      /* fcu_picture_report: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   DevBuf hash;                     /* fcu_picture_hash: plane pointers, hash records, per-chunk partials */
   DevBuf score;                    /* fcu_label_score / fcu_trace_maps: picture descriptors, picture records, per-CTU records (when the caller gives none) */
+  DevBuf risk;                     /* fcu_risk_train / fcu_risk_predict / fcu_nobf_maps: pointer arrays, the dropped counter, one table slot per workgroup */
   DevBuf maps;                     /* fcu_decision_maps / fcu_split_match: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
    * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
@@ -206,6 +208,7 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_CU_TRACE: return (int)sizeof(fcu_cu_trace);
   case FCU_ABI_CTU_SCORE: return (int)sizeof(fcu_ctu_score);
   case FCU_ABI_PIC_SCORE: return (int)sizeof(fcu_pic_score);
+  case FCU_ABI_RISK_MODEL: return (int)sizeof(fcu_risk_model);
   default: return -1;
   }
 }
@@ -240,7 +243,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p); hipFree(c->score.p);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p); hipFree(c->score.p); hipFree(c->risk.p);
   hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
@@ -1060,5 +1063,79 @@ int fcu_feature_maps(fcu_ctx *c, int n_pics, int sets, const uint8_t *const *dev
   if (kernel_ms) ev.ms(kernel_ms, 0, 1);
   return FCU_OK;
 }
+
+/* the risk-table model: risk_train + risk_add, risk_predict, nobf_blocks (fcu_risk.h) */
+int fcu_risk_train(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace, const uint16_t *const *dev_keys, fcu_risk_model *dev_model, int accumulate,
+                   uint32_t *host_dropped, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_risk_train: null context");
+  { std::string err; const int rc = risk_train_args_check(n_pics, dev_trace, dev_keys, dev_model, accumulate, c->hs.label_count(), err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const int n_units = G.n_ctu * n_pics, n_groups = risk_train_groups(n_units);
+  const size_t o_tr = 0, o_key = up(o_tr + sizeof(void *) * n_pics), o_drop = up(o_key + sizeof(void *) * n_pics), o_slots = up(o_drop + sizeof(uint32_t)),
+               total = o_slots + sizeof(RiskSlot) * (size_t)n_groups;
+  HIPCHK(c->risk.reserve(total, st));
+  uint8_t *base = (uint8_t *)c->risk.p;
+  const fcu_cu_trace **d_tr = (const fcu_cu_trace **)(base + o_tr); const uint16_t **d_key = (const uint16_t **)(base + o_key);
+  uint32_t *d_drop = (uint32_t *)(base + o_drop); RiskSlot *d_slots = (RiskSlot *)(base + o_slots);
+  HIPCHK(hipMemcpyAsync(d_tr, dev_trace, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_key, dev_keys, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(risk_train, dim3((unsigned)n_groups), dim3(RISK_THREADS), 0, st, d_tr, d_key, d_slots, G, n_units, n_groups);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  hipLaunchKernelGGL(risk_add, dim3(RISK_ADD_GROUPS), dim3(RISK_ADD_THREADS), 0, st, d_slots, n_groups, dev_model, d_drop, accumulate);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(2));
+  uint32_t dropped = 0;
+  HIPCHK(hipMemcpyAsync(&dropped, d_drop, sizeof(dropped), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* dev_trace, dev_keys (the caller's arrays) and `dropped` are done with */
+  if (host_dropped) *host_dropped = dropped;
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
+  return FCU_OK;
+}
+
+int fcu_risk_predict(fcu_ctx *c, int n_pics, const uint16_t *const *dev_keys, const fcu_risk_model *dev_model, int min_count, int8_t *dev_labels, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_risk_predict: null context");
+  { std::string err; const int rc = risk_predict_args_check(n_pics, dev_keys, dev_model, min_count, dev_labels, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const RiskPlan P = risk_plan(G);
+  HIPCHK(c->risk.reserve(up(sizeof(void *) * n_pics), st));
+  const uint16_t **d_key = (const uint16_t **)c->risk.p;
+  HIPCHK(hipMemcpyAsync(d_key, dev_keys, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(risk_predict, dim3((unsigned)P.wg_off[4], (unsigned)n_pics), dim3(RISK_PRED_THREADS), 0, st, d_key, dev_model, min_count, dev_labels, G, P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));                          /* dev_keys (the caller's array) is done with */
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+int fcu_nobf_maps(fcu_ctx *c, int n_pics, const int16_t *const *dev_obf, uint16_t *dev_nobf, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_nobf_maps: null context");
+  { std::string err; const int rc = nobf_args_check(n_pics, dev_obf, dev_nobf, err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const RiskPlan P = risk_plan(G);
+  HIPCHK(c->risk.reserve(up(sizeof(void *) * n_pics), st));
+  const int16_t **d_obf = (const int16_t **)c->risk.p;
+  HIPCHK(hipMemcpyAsync(d_obf, dev_obf, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(nobf_blocks, dim3((unsigned)P.wg_off[4], (unsigned)n_pics), dim3(RISK_PRED_THREADS), 0, st, d_obf, dev_nobf, G, P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));                          /* dev_obf (the caller's array) is done with */
+  return FCU_OK;
+}
+
+void fcu_risk_table(const fcu_risk_model *host_model, int min_count, int8_t table[4][FCU_RISK_BINS]) { risk_table(host_model, min_count, table); }
 
 } /* extern "C" */

@@ -114,6 +114,14 @@ __device__ static inline void maps_put(void *dst, const void *src)
   }
 }
 
+/* what N_OBF counts: "partition (x4, y4) lies inside the picture and its count in the OBF map is > 0".  One definition, shared by
+ * maps_ctu and by the kernel of fcu_nobf_maps (fcu_risk.h) */
+__device__ static inline uint16_t maps_obf_flag(const int16_t *obf, int W4, int H4, int x4, int y4)
+{
+  const bool in = x4 < W4 && y4 < H4;
+  return (uint16_t)(in && ((const FCU_HBM int16_t *)obf)[(size_t)y4 * W4 + x4] > 0 ? 1 : 0);
+}
+
 /* N_OBF of level D: node sums four values of the level below */
 template <int D>
 __device__ static inline void maps_nobf_level(MapsLds &L, const MapsGeom &G, uint16_t *nobf, int cx, int cy, int t)
@@ -150,9 +158,7 @@ __device__ static inline void maps_ctu_phase(MapsLds &L, const MapsPic *pics, co
     }
     if (Q.mv) { const int16_t hor = O.mv[t][0], ver = O.mv[t][1]; L.mv[r][0] = hor; L.mv[r][1] = ver; }
     if (Q.nobf) {
-      const int x4 = cx * 16 + (r & 15), y4 = cy * 16 + (r >> 4);
-      const bool in = x4 < W4 && y4 < H4;
-      L.flag[t] = (uint16_t)(in && ((const FCU_HBM int16_t *)P.obf)[(size_t)y4 * W4 + x4] > 0 ? 1 : 0);
+      L.flag[t] = maps_obf_flag(P.obf, W4, H4, cx * 16 + (r & 15), cy * 16 + (r >> 4));
     }
     if (Q.labels && t < MAPS_NODES) {
       const MapsNode N = maps_node(t);

@@ -184,7 +184,8 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_tile_grid", "fcu_tile_chains", "fcu_tiles_begin", "fcu_wpp_begin_tiles", "fcu_deblock_tiles", "fcu_sao_tiles", "fcu_picture_report",
            "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices",
            "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters",
-           "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps", "fcu_feature_count", "fcu_feature_maps"]
+           "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps", "fcu_feature_count", "fcu_feature_maps",
+           "fcu_risk_train", "fcu_risk_predict", "fcu_nobf_maps", "fcu_risk_table"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -199,6 +200,20 @@ CU_TRACE_DTYPE = np.dtype([("j0", np.float64), ("j1", np.float64), ("valid", np.
                            ("split_tried", np.uint8), ("pad", np.uint8, (4,))])                                                    # fcu_cu_trace
 CTU_SCORE_DTYPE = np.dtype([("n", np.uint16, (4, 4)), ("open", np.uint16, (4,)), ("pad", np.uint16, (12,)), ("loss", np.float64, (4, 2))])   # fcu_ctu_score
 PIC_SCORE_DTYPE = np.dtype([("v", np.float64, (4, 6)), ("open", np.uint32, (4,)), ("scored", np.uint32, (4,))])                    # fcu_pic_score
+
+RISK_BINS = 257                                            # FCU_RISK_BINS: N_OBF of a 64x64 CU is 0..256
+RISK_MODEL_DTYPE = np.dtype([("risk", np.int64, (4, RISK_BINS, 2)), ("count", np.uint32, (4, RISK_BINS, 2))])                      # fcu_risk_model
+
+
+def risk_table(model, min_count=1):
+    """fcu_risk_table: the rule of the risk-table model on a host copy of one (a RISK_MODEL_DTYPE array, or the uint8 bytes of one)
+    -> int8 [4, 257]: LABEL_NOT_SPLIT where risk[d][x][1] < risk[d][x][0], else LABEL_SPLIT; LABEL_ABSENT for a bin with fewer than
+    min_count samples.  Host arithmetic of libfcu.so; needs no GPU."""
+    m = np.ascontiguousarray(model).view(np.uint8).reshape(-1)
+    assert m.size == RISK_MODEL_DTYPE.itemsize and min_count >= 0, "risk_table: one fcu_risk_model and a non-negative min_count"
+    out = np.zeros((4, RISK_BINS), np.int8)
+    load_lib().fcu_risk_table(m.ctypes.data, int(min_count), out.ctypes.data)
+    return out
 
 
 # FCU_FEATSET_*: the feature sets of fcu_feature_maps, in column order, and the names of their columns (include/fcu.h):
@@ -330,6 +345,11 @@ def load_lib():
     lib.fcu_trace_maps.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_feature_count.argtypes = [C.c_int]
     lib.fcu_feature_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_risk_train.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_risk_predict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_nobf_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fcu_risk_table.restype = None
+    lib.fcu_risk_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -817,6 +837,66 @@ class CuEngine:
         self._chk(self.lib.fcu_trace_maps(self.h, n, tp, ptr(d_lab), ptr(d_j0), ptr(d_j1), C.byref(ms) if timed else None, s), "fcu_trace_maps")
         res = {k: v for k, v in (("labels", d_lab), ("j0", d_j0), ("j1", d_j1)) if v is not None}
         return (res, float(ms.value)) if timed else res
+
+    # -- the risk-table model: trained on CU traces and run on the device
+    def _key_ptrs(self, keys, who):
+        n = len(keys)
+        rows = [keys[i] for i in range(n)]
+        for t in rows:
+            assert t.is_cuda and t.dtype in (self.torch.uint16, self.torch.int16) and t.is_contiguous() and t.numel() == self.label_count(), who + ": uint16 [NL] keys on the device"
+        return (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in rows]), rows
+
+    def risk_train(self, traces, keys, model=None, accumulate=False, timed=False, stream=None):
+        """Trains the risk-table model on the CU traces of exhaustively decided pictures (fcu_risk_train; definition: include/fcu.h).
+        traces: list of trace tensors (enable_cu_trace; result dicts with "cu_trace" qualify); keys: a uint16 device tensor [n, NL]
+        or a list of [NL] tensors -- nobf_maps(obf), or any feature quantised to 0..256 -- block for block aligned with trace_maps.
+        model: the uint8 device tensor of one fcu_risk_model to write (accumulate=False: overwritten, nothing to clear) or to add
+        the batch to (accumulate=True); None: a new one.  Returns (model, dropped): dropped = samples whose key was >= 257.
+        timed=True: also the durations (ms) of the two kernels."""
+        torch = self.torch
+        n = len(traces)
+        assert len(keys) == n
+        tp = self._trace_ptrs(traces, "risk_train")
+        kp, keep = self._key_ptrs(keys, "risk_train")
+        if model is None:
+            assert not accumulate, "risk_train: accumulate=True adds to a model"
+            model = torch.empty(RISK_MODEL_DTYPE.itemsize, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        assert model.is_cuda and model.dtype == torch.uint8 and model.is_contiguous() and model.numel() == RISK_MODEL_DTYPE.itemsize, "risk_train: one fcu_risk_model as uint8 on the device"
+        dropped = C.c_uint32(0)
+        ms = (C.c_float * 2)() if timed else None
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_risk_train(self.h, n, tp, kp, model.data_ptr(), 1 if accumulate else 0, C.byref(dropped), ms, s), "fcu_risk_train")
+        return (model, int(dropped.value), (ms[0], ms[1])) if timed else (model, int(dropped.value))
+
+    def risk_predict(self, keys, model, min_count=1, timed=False, stream=None):
+        """The model's labels for pictures that need not be decided yet (fcu_risk_predict): keys as in risk_train, model the tensor
+        risk_train returned.  Returns the int8 device tensor [n, NL]; row i is what set_labels takes: LABEL_FORCED where the picture
+        edge cuts the block, LABEL_ABSENT for a key >= 257 or a bin with fewer than min_count samples, else the rule.  timed=True:
+        (tensor, kernel ms)."""
+        torch = self.torch
+        kp, keep = self._key_ptrs(keys, "risk_predict")
+        n = len(keep)
+        assert model.is_cuda and model.dtype == torch.uint8 and model.is_contiguous() and model.numel() == RISK_MODEL_DTYPE.itemsize, "risk_predict: one fcu_risk_model as uint8 on the device"
+        out = torch.empty((n, self.label_count()), dtype=torch.int8, device=model.device)
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_risk_predict(self.h, n, kp, model.data_ptr(), int(min_count), out.data_ptr(), C.byref(ms) if timed else None, s), "fcu_risk_predict")
+        return (out, float(ms.value)) if timed else out
+
+    def nobf_maps(self, obf, stream=None):
+        """The N_OBF maps of pictures that have not been decided (fcu_nobf_maps): obf = an int16 device tensor [n, height / 4,
+        width / 4] (or one map, or a list of maps) of obf_prepass.  Returns the uint16 device tensor [n, NL]: the bytes
+        decision_maps(..., obf=...)["n_obf"] flattened."""
+        torch = self.torch
+        maps = [obf] if torch.is_tensor(obf) and obf.dim() == 2 else [obf[i] for i in range(len(obf))]
+        for t in maps:
+            assert t.is_cuda and t.dtype == torch.int16 and t.is_contiguous() and tuple(t.shape) == (self.height // 4, self.width // 4), "nobf_maps: int16 [height / 4, width / 4] on the device"
+        n = len(maps)
+        out = torch.empty((n, self.label_count()), dtype=torch.uint16, device=torch.device("cuda", self.device))
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in maps])
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_nobf_maps(self.h, n, ptrs, out.data_ptr(), s), "fcu_nobf_maps")
+        return out
 
     # -- getTMVFeature / FormFeatureVector(SOC)
     def feature_maps(self, lumas, sets=("tmv", "soc"), yc=None, timed=False, stream=None):

@@ -96,7 +96,7 @@ class SequenceDecider:
     """All-intra sequence, picture by picture, on one GPU.  `fast=False` keeps every picture in the Training state
     (plain HM RDO); `fast=True` runs the fork's Training / Verifying / Testing cycle with its default (Naive) control."""
 
-    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, cu_trace=False, features=None, **flags):
+    def __init__(self, width, height, qp, slice_ctus=None, fast=True, deblock=True, device=0, schedule=None, in_flight=1, wpp=False, slice_rows=None, tiles=None, lf_cross_tiles=None, report=False, pic_hash=None, maps=None, lf_cross_slices=None, labels=None, cu_trace=False, features=None, risk=None, **flags):
         """cu_trace=True: every Training picture (all of them with fast=False) is decided with a CU trace bound to its chains
         (CuEngine.enable_cu_trace): its result dict gains `cu_trace`, the device tensor of n_ctu x 85 fcu_cu_trace records -- J0, J1 and
         the outcome of every CU the exhaustive search visited; CuEngine.trace_maps and CuEngine.label_score take it as it is.
@@ -135,13 +135,38 @@ class SequenceDecider:
         float32 device tensor [NL, F] of CuEngine.feature_maps -- the fork's TMV / SOC model inputs of every block, row for row
         aligned with the label / N_OBF maps and with CuEngine.trace_maps of `cu_trace` -- formed in one batched call per group from
         the source planes the chains were bound with.  With "soc" the OBF pre-pass runs for Training pictures too (it already runs
-        for the others) to get the picture's thresholds; a Training chain is not given the map, so no decision changes."""
+        for the others) to get the picture's thresholds; a Training chain is not given the map, so no decision changes.
+        risk=True, or a dict with min_count (default 1) and / or key (with fast=True, not together with labels): the fork's schedule
+        on the risk-table model (include/fcu.h), nothing leaving the device.  Every Training picture is decided with a CU trace
+        bound (as cu_trace=True does) and gets its OBF pre-pass; after the launch of a Training group CuEngine.risk_train adds the
+        group's traces to the model -- overwriting it at the first Training group of a period.  The keys are
+        CuEngine.nobf_maps(obf), or key(poc, planes, obf, n_obf) -> uint16 device tensor [NL].  Every Verifying and Testing
+        picture gets CuEngine.risk_predict on its own keys and the labels bound to all its chains: the Verifying counters,
+        fcu_decision_switch and the per-depth switches work on them unchanged.  The result dicts of such pictures carry `labels`;
+        `risk_model` is the model's device tensor (None before the first Training group)."""
+        if risk is None or risk is False:
+            self.risk = None
+        else:
+            if risk is not True and (not isinstance(risk, dict) or set(risk) - {"min_count", "key"}):
+                raise ValueError("SequenceDecider: risk is None, True or a dict with min_count / key")
+            self.risk = {"min_count": 1, "key": None}
+            self.risk.update({} if risk is True else risk)
+            mc = self.risk["min_count"]
+            if not isinstance(mc, (int, np.integer)) or isinstance(mc, bool) or mc < 0:
+                raise ValueError("SequenceDecider: risk min_count is a non-negative integer")
+            if self.risk["key"] is not None and not callable(self.risk["key"]):
+                raise ValueError("SequenceDecider: risk key is a callable key(poc, planes, obf, n_obf) -> uint16 device tensor [NL]")
+            if not fast:
+                raise ValueError("SequenceDecider: risk needs fast=True (the model is trained on the Training pictures of the schedule)")
+            if labels is not None:
+                raise ValueError("SequenceDecider: risk and labels both name the model of the Verifying / Testing pictures; give one")
+        self.risk_model = None
         self.do_report = report
         self.features = None if features is None or features is False else _engine.feature_sets(("tmv", "soc") if features is True else features)[1]
         if labels is not None and not callable(labels):
             raise ValueError("SequenceDecider: labels is a callable labels(poc, planes, obf) -> int8 device tensor [NL] or None")
         self.labels = labels
-        self.cu_trace = bool(cu_trace)
+        self.cu_trace = bool(cu_trace) or self.risk is not None
         self.maps = engine_maps_options(maps, ("depth", "part_size", "pred_mode", "intra_dir_luma"), "SequenceDecider")
         if pic_hash is not None and pic_hash not in _engine.HASH_KINDS:
             raise ValueError("SequenceDecider: pic_hash is None, 'md5', 'crc' or 'checksum'")
@@ -191,6 +216,10 @@ class SequenceDecider:
                 for k in range(n_sl):
                     eng.set_decision(first + k, state, obf, sk, te)
                 lab = self.labels(poc, eng.org_planes(first), obf) if self.labels is not None else None
+                if self.risk is not None:
+                    if self.risk_model is None:
+                        raise ValueError("SequenceDecider: risk has no model yet: the schedule needs at least one Training picture per period")
+                    lab = eng.risk_predict(self._risk_keys(poc, first, obf)[None], self.risk_model, self.risk["min_count"])[0]
                 if lab is not None:                            # labels are per picture: every chain of it takes the one array
                     eng.set_labels(range(first, first + n_sl), lab)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
@@ -199,6 +228,8 @@ class SequenceDecider:
                 for k in range(1, n_sl):
                     eng.enable_cu_trace(first + k, tr)
                 pics[-1]["cu_trace"] = tr
+                if self.risk is not None:                      # the keys of a Training picture: its own pre-pass; the chains are not given the map
+                    pics[-1]["risk_keys"] = self._risk_keys(poc, first, eng.obf_prepass(eng.org_planes(first)[0])[0][0].contiguous())
             if state != TRAINING and lab is not None:
                 pics[-1]["labels"] = lab
             if self.maps and state != TRAINING:
@@ -207,6 +238,9 @@ class SequenceDecider:
                 pics[-1]["yc"] = yc[0] if yc is not None else eng.obf_prepass(eng.org_planes(first)[0])[1][0]
         eng.compress_pictures(0, len(yuvs), self.layout)
         nb = _engine.CTU_OUT_BYTES
+        if self.risk is not None and pics[0]["state"] == TRAINING:      # the pictures of a group share their state
+            first_group = pics[0]["poc"] % self.schedule.period == 0
+            self.risk_model, _ = eng.risk_train(pics, [p.pop("risk_keys") for p in pics], model=None if first_group else self.risk_model, accumulate=not first_group)
         for p in pics:
             p["verify"] = eng.verify_counts(p["first"], self.n_slices) if p["state"] == VERIFYING else None
             if self.fast:
@@ -234,6 +268,16 @@ class SequenceDecider:
             p["tu_trials"] = sum(eng.debug_counters(p["first"] + k)[16] for k in range(self.n_slices))
         self.poc += len(yuvs)
         return pics
+
+    def _risk_keys(self, poc, first, obf):
+        """the uint16 [NL] key array of a picture: its N_OBF map, or what the caller's key function makes of it"""
+        n_obf = self.eng.nobf_maps(obf)[0]
+        if self.risk["key"] is None:
+            return n_obf
+        k = self.risk["key"](poc, self.eng.org_planes(first), obf, n_obf)
+        if not (k.is_cuda and k.dtype == n_obf.dtype and k.is_contiguous() and k.numel() == n_obf.numel()):
+            raise ValueError("SequenceDecider: risk key returns a contiguous uint16 device tensor [NL]")
+        return k
 
     def close(self):
         self.eng.destroy()

@@ -681,6 +681,61 @@ int  fcu_feature_count(int sets);
 int  fcu_feature_maps(fcu_ctx *c, int n_pics, int sets, const uint8_t *const *dev_y, const double *host_yc,
                       float *dev_features, float *kernel_ms, void *hip_stream);
 
+/* ---- risk-table model: a model between fcu_trace_maps and fcu_chain_set_labels that is trained and run on the device.
+ * The fork's BayesDecision (tools_YS.cpp:709-725) looks up two risks by the CU's N_OBF, R0 = g_dJdx01[depth][x] and
+ * R1 = g_dJdx10[depth][x], and predicts TerminateCU when R0 < R1, Skip2Nx2N otherwise; BayesNew sizes the tables {257, 65, 17, 5}
+ * per depth (:906).  The decision rule and the table sizes are the fork's.  The fork never fills the tables (g_dJdx01 has no
+ * definition in its tree): the training rule below is this library's.
+ *   sample   a trace record with valid, split_tried and whole_tried all set (the samples of fcu_label_score whose j0 is a real
+ *            cost, never FCU_MAX_DOUBLE).  A CU the picture edge cuts has no record and is no sample.
+ *   key      the record of CTU a, depth d, z-index z is the block at off(d) + (y / s) * BW(d) + x / s of the label-map layout (the
+ *            addressing of fcu_trace_maps and fcu_chain_set_labels); its key is the uint16 at that element of the picture's key
+ *            array, uint16 [NL] -- the N_OBF map (fcu_decision_maps, fcu_nobf_maps) or any feature of the caller's quantised to
+ *            0..256.  A sample whose key is >= FCU_RISK_BINS is dropped and counted in `dropped`.
+ *   q        the quantised loss (int64) floor(fabs(j0 - j1) * 256.0), clamped to 2^40 - 1; a value that is not < 2^40, NaN
+ *            included, gives 2^40 - 1.  The multiplication is exact and fabs is countRDLoss' (tools_YS.cpp:980-986).
+ *   model    risk[d][x][t] = sum of q, count[d][x][t] = number, over the samples of depth d and key x with split_won == t.
+ *            risk[d][x][0] is what predicting SPLIT on bin x loses (its not-split samples become false positives: FPLoss),
+ *            risk[d][x][1] what predicting NOT_SPLIT loses (FNLoss).
+ *   rule     FCU_LABEL_NOT_SPLIT iff risk[d][x][1] < risk[d][x][0], else FCU_LABEL_SPLIT (a tie gives SPLIT: the fork's
+ *            R0 < R1 -> -1, else +1); a bin with count[d][x][0] + count[d][x][1] < min_count gives FCU_LABEL_ABSENT, no
+ *            prediction.  min_count 0 is the fork's rule on every bin: an empty bin predicts SPLIT.
+ * Every accumulated quantity is an integer: sums commute, so the model is the same bytes whatever order the kernels visit the
+ * records in, and no tolerance, iteration count or summation order enters the interface.  Capacity: q < 2^40, so 2^23 samples per
+ * bin before a sum could wrap -- the caller's to respect across accumulating calls; one call takes at most 2^22 blocks
+ * (n_pics * NL).  The structure has no implicit padding and lives in HBM at a multiple of 8 bytes.
+ *
+ * fcu_risk_train: dev_trace / dev_keys are host arrays of n_pics device pointers (a picture's fcu_cu_trace array and its key array).
+ * accumulate 0: dev_model is overwritten -- the caller clears nothing; accumulate 1: the batch is added to what dev_model holds:
+ * pictures A then B with accumulate 1 give the bytes of [A, B] in one call.  host_dropped (may be NULL) receives the samples this
+ * call dropped.  Two kernels: one pass over the records, every workgroup adding its samples into a table of its own in LDS (integer
+ * LDS adds) and storing it to its slot of a context buffer; then one thread per table entry adds the slots and writes, or adds to,
+ * dev_model.  No global atomics, nothing to clear: a repeated call gives identical bytes.  The call returns after the kernels have
+ * finished; kernel_ms2 (may be NULL) receives their durations.
+ * fcu_risk_predict: dev_labels int8 [n_pics][NL], ready for fcu_chain_set_labels: a block the picture edge cuts (d < 3) gets
+ * FCU_LABEL_FORCED whatever its key (the rule of fcu_trace_maps), a key >= FCU_RISK_BINS gets FCU_LABEL_ABSENT, everything else the
+ * rule above.  dev_model is read on the device; one kernel, one thread per block, every output byte written by exactly one
+ * thread; the call returns after it has finished, kernel_ms (may be NULL) receives its duration.
+ * fcu_nobf_maps: the N_OBF map uint16 [n_pics][NL] of pictures that have not been decided (a Testing picture's keys are needed
+ * before its fcu_ctu_out exists): the bytes fcu_decision_maps(..., dev_obf, dev_nobf) gives.  One kernel on `hip_stream`, one thread per block;
+ * the call returns after it has finished.
+ * fcu_risk_table: the rule on a host copy of a model (host arithmetic, needs no GPU).
+ * FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1; a NULL array or a NULL entry of one; a NULL or misaligned
+ * dev_model; dev_keys / dev_nobf at an odd byte; a negative min_count; n_pics * NL > 2^22 (fcu_risk_train).  No CPU fallback. */
+#define FCU_RISK_BINS 257            /* N_OBF of a 64x64 CU is 0..256 */
+#define FCU_RISK_Q_MAX ((int64_t)1099511627775)      /* 2^40 - 1 */
+#define FCU_RISK_MAX_BLOCKS (1 << 22)                /* n_pics * NL of one fcu_risk_train call */
+typedef struct fcu_risk_model {      /* 24 672 B, no implicit padding; lives in HBM, 8-byte aligned */
+  int64_t  risk [4][FCU_RISK_BINS][2];   /* [depth][key][truth]: sum of q over the samples of that bin whose split_won == truth */
+  uint32_t count[4][FCU_RISK_BINS][2];   /* samples of that bin with split_won == truth */
+} fcu_risk_model;
+int  fcu_risk_train(fcu_ctx *c, int n_pics, const fcu_cu_trace *const *dev_trace, const uint16_t *const *dev_keys,
+                    fcu_risk_model *dev_model, int accumulate, uint32_t *host_dropped, float *kernel_ms2, void *hip_stream);
+int  fcu_risk_predict(fcu_ctx *c, int n_pics, const uint16_t *const *dev_keys, const fcu_risk_model *dev_model, int min_count,
+                      int8_t *dev_labels, float *kernel_ms, void *hip_stream);
+int  fcu_nobf_maps(fcu_ctx *c, int n_pics, const int16_t *const *dev_obf, uint16_t *dev_nobf, void *hip_stream);
+void fcu_risk_table(const fcu_risk_model *host_model, int min_count, int8_t table[4][FCU_RISK_BINS]);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -717,7 +772,7 @@ const char *fcu_build_info(void);
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
        FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9,
        FCU_ABI_PIC_HASH = 10, FCU_ABI_CTU_MATCH = 11, FCU_ABI_PIC_MATCH = 12, FCU_ABI_CU_TRACE = 13, FCU_ABI_CTU_SCORE = 14,
-       FCU_ABI_PIC_SCORE = 15 };
+       FCU_ABI_PIC_SCORE = 15, /* 16 is not assigned and stays unknown */ FCU_ABI_RISK_MODEL = 17 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus
