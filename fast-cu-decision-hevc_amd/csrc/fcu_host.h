@@ -489,6 +489,16 @@ FCU_HOST_DEV inline int64_t risk_q(double j0, double j1)
   const double s = fabs(j0 - j1) * 256.0;                    /* (exact: a power of two) */
   return s < 1099511627776.0 ? (int64_t)floor(s) : FCU_RISK_Q_MAX;
 }
+/* the sample test and the quantised loss of a trace record as the key tree (fcu_tree.h) takes them: true for a record with valid,
+ * split_tried and whole_tried all set; *q (q may be null: the test alone) receives risk_q.  risk_train (fcu_risk.h) keeps its own
+ * spelling of the same test next to the same risk_q: calling this function there changed its compiled code (register allocation
+ * of the whole kernel) in every form tried, and that kernel must stay what it was.  tests/test_tree.py holds the two sample sets
+ * against each other: the histograms summed over bins equal the model risk_train gives on the node array */
+FCU_HOST_DEV inline bool risk_sample(uint32_t valid, uint32_t split_tried, uint32_t whole_tried, double j0, double j1, int64_t *q)
+{
+  if (q) *q = risk_q(j0, j1);
+  return valid != 0 && split_tried != 0 && whole_tried != 0;
+}
 /* the fork's R0 < R1 -> TerminateCU, else Skip2Nx2N: r0 = risk[..][0] (the loss of predicting SPLIT), r1 = risk[..][1] */
 FCU_HOST_DEV inline int risk_rule(int64_t r0, int64_t r1, uint32_t c0, uint32_t c1, int min_count)
 {
@@ -549,6 +559,164 @@ inline int nobf_args_check(int n_pics, const int16_t *const *dev_obf, const void
   else if ((uintptr_t)dev_nobf & 1) bad = "dev_nobf starts at an even byte";
   if (bad) { err = who + bad; return FCU_ERR_ARG; }
   return risk_null_entry(who, "dev_obf", (const void *const *)dev_obf, n_pics, err);
+}
+/* ---- the key tree (include/fcu.h): what its calls refuse, with the argument named, and the split choice (fcu_tree_split) */
+static_assert(sizeof(fcu_key_tree) == 376 && sizeof(fcu_key_tree) % 8 == 0 && offsetof(fcu_key_tree, feature) == 4 && offsetof(fcu_key_tree, thr) == 252,
+              "fcu_key_tree has no implicit padding and is a multiple of 8 bytes");
+/* fcu_feature_edges_check: every row of 31 edges finite and non-decreasing */
+inline int tree_edges_check(const float *edges, int sets, std::string &err)
+{
+  const std::string who = "fcu_feature_edges_check: ";
+  const int F = feature_count(sets);
+  if (F < 0) { err = who + "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC"; return FCU_ERR_ARG; }
+  if (!edges) { err = who + "host_edges is null"; return FCU_ERR_ARG; }
+  for (int r = 0; r < 4 * F; r++) {
+    const float *e = edges + (size_t)r * (FCU_TREE_BINS - 1);
+    for (int k = 0; k < FCU_TREE_BINS - 1; k++)
+      if (!(e[k] - e[k] == 0.0f) || (k > 0 && e[k] < e[k - 1])) {      /* (x - x is 0 for a finite x only) */
+        err = who + "host_edges[" + std::to_string(r / F) + "][" + std::to_string(r % F) + "] is not finite and non-decreasing at " + std::to_string(k);
+        return FCU_ERR_ARG;
+      }
+  }
+  return FCU_OK;
+}
+/* a tree the kernels may walk: levels 0..5, every column -1..F-1, every threshold 0..30 */
+inline const char *tree_bad(const fcu_key_tree *t, int F)
+{
+  if (!t) return "host_tree is null";
+  if (t->levels < 0 || t->levels > FCU_TREE_MAX_LEVELS) return "host_tree->levels is 0 .. FCU_TREE_MAX_LEVELS";
+  for (int d = 0; d < 4; d++) for (int i = 0; i < FCU_TREE_NODES; i++) {
+    if (t->feature[d][i] < -1 || t->feature[d][i] >= F) return "host_tree->feature holds -1 or a column of the feature sets";
+    if (t->thr[d][i] > FCU_TREE_BINS - 2) return "host_tree->thr is 0 .. 30";
+  }
+  return nullptr;
+}
+inline int feature_bins_args_check(int n_pics, int sets, const void *dev_features, const void *dev_edges, const void *dev_bins, int n_blocks, std::string &err)
+{
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (feature_count(sets) < 0) bad = "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC";
+  else if (!dev_features) bad = "dev_features is null";
+  else if ((uintptr_t)dev_features & 3) bad = "dev_features starts at a multiple of 4 bytes";
+  else if (!dev_edges) bad = "dev_edges is null";
+  else if ((uintptr_t)dev_edges & 3) bad = "dev_edges starts at a multiple of 4 bytes";
+  else if (!dev_bins) bad = "dev_bins is null";
+  else if ((int64_t)n_pics * n_blocks > FCU_RISK_MAX_BLOCKS) bad = "n_pics * NL is at most 2^22 in one call";
+  if (bad) { err = std::string("fcu_feature_bins: ") + bad; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int tree_keys_args_check(int n_pics, int sets, const void *dev_bins, const fcu_key_tree *tree, int levels, const void *dev_keys, int n_blocks, std::string &err)
+{
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (feature_count(sets) < 0) bad = "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC";
+  else if (!dev_bins) bad = "dev_bins is null";
+  else if (tree_bad(tree, feature_count(sets))) bad = tree_bad(tree, feature_count(sets));
+  else if (levels < 0 || levels > tree->levels) bad = "levels is 0 .. host_tree->levels";
+  else if (!dev_keys) bad = "dev_keys is null";
+  else if ((uintptr_t)dev_keys & 1) bad = "dev_keys starts at an even byte";
+  else if ((int64_t)n_pics * n_blocks > FCU_RISK_MAX_BLOCKS) bad = "n_pics * NL is at most 2^22 in one call";
+  if (bad) { err = std::string("fcu_tree_keys: ") + bad; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int tree_hist_args_check(int n_pics, int sets, int level, const fcu_cu_trace *const *dev_trace, const uint8_t *const *dev_bins, const uint16_t *const *dev_nodes,
+                                const void *dev_risk, const void *dev_count, int accumulate, int n_blocks, std::string &err)
+{
+  const std::string who = "fcu_tree_hist: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (feature_count(sets) < 0) bad = "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC";
+  else if (level < 0 || level >= FCU_TREE_MAX_LEVELS) bad = "level is 0 .. FCU_TREE_MAX_LEVELS - 1";
+  else if (!dev_trace) bad = "dev_trace is null";
+  else if (!dev_bins) bad = "dev_bins is null";
+  else if (!dev_nodes && level > 0) bad = "dev_nodes is null although level > 0";
+  else if (!dev_risk) bad = "dev_risk is null";
+  else if ((uintptr_t)dev_risk & 7) bad = "dev_risk starts at a multiple of 8 bytes";
+  else if (!dev_count) bad = "dev_count is null";
+  else if ((uintptr_t)dev_count & 3) bad = "dev_count starts at a multiple of 4 bytes";
+  else if (accumulate != 0 && accumulate != 1) bad = "accumulate is 0 or 1";
+  else if ((int64_t)n_pics * n_blocks > FCU_RISK_MAX_BLOCKS) bad = "n_pics * NL is at most 2^22 in one call";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  if (risk_null_entry(who, "dev_trace", (const void *const *)dev_trace, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  if (risk_null_entry(who, "dev_bins", (const void *const *)dev_bins, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  if (dev_nodes && risk_null_entry(who, "dev_nodes", (const void *const *)dev_nodes, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  for (int i = 0; dev_nodes && i < n_pics; i++) if ((uintptr_t)dev_nodes[i] & 1) { err = who + "dev_nodes[" + std::to_string(i) + "] starts at an even byte"; return FCU_ERR_ARG; }
+  return FCU_OK;
+}
+inline int tree_train_args_check(int n_pics, int sets, int levels, int min_count, const fcu_cu_trace *const *dev_trace, const uint8_t *const *dev_bins, const fcu_key_tree *tree,
+                                 int n_blocks, std::string &err)
+{
+  const std::string who = "fcu_tree_train: ";
+  const char *bad = nullptr;
+  if (n_pics < 1) bad = "n_pics must be at least 1";
+  else if (feature_count(sets) < 0) bad = "sets is a non-empty mask of FCU_FEATSET_TMV | FCU_FEATSET_SOC";
+  else if (levels < 0 || levels > FCU_TREE_MAX_LEVELS) bad = "levels is 0 .. FCU_TREE_MAX_LEVELS";
+  else if (min_count < 0) bad = "min_count must not be negative";
+  else if (!dev_trace) bad = "dev_trace is null";
+  else if (!dev_bins) bad = "dev_bins is null";
+  else if (!tree) bad = "host_tree is null";
+  else if ((int64_t)n_pics * n_blocks > FCU_RISK_MAX_BLOCKS) bad = "n_pics * NL is at most 2^22 in one call";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  if (risk_null_entry(who, "dev_trace", (const void *const *)dev_trace, n_pics, err) != FCU_OK) return FCU_ERR_ARG;
+  return risk_null_entry(who, "dev_bins", (const void *const *)dev_bins, n_pics, err);
+}
+/* fcu_tree_train's first step: a tree of `levels` levels with no node split */
+inline void tree_clear(fcu_key_tree &t, int levels)
+{
+  t.levels = levels;
+  for (int d = 0; d < 4; d++) for (int i = 0; i < FCU_TREE_NODES; i++) { t.feature[d][i] = -1; t.thr[d][i] = 0; }
+}
+/* fcu_tree_split: the nodes of `level` from that level's histograms, [4][2^level][F][32][2] each */
+inline int tree_split(const int64_t *risk, const uint32_t *count, int F, int level, int min_count, fcu_key_tree *tree, std::string &err)
+{
+  const std::string who = "fcu_tree_split: ";
+  const char *bad = nullptr;
+  if (!risk) bad = "host_risk is null";
+  else if (!count) bad = "host_count is null";
+  else if (F < 1 || F > FCU_FEAT_TMV + FCU_FEAT_SOC) bad = "F is 1 .. 146";
+  else if (level < 0 || level >= FCU_TREE_MAX_LEVELS) bad = "level is 0 .. FCU_TREE_MAX_LEVELS - 1";
+  else if (min_count < 0) bad = "min_count must not be negative";
+  else if (!tree) bad = "tree is null";
+  if (bad) { err = who + bad; return FCU_ERR_ARG; }
+  const int B = FCU_TREE_BINS, n_nodes = 1 << level;
+  const int64_t need = min_count > 1 ? min_count : 1;
+  /* the totals of every node, summed over every column, must agree before anything is written */
+  for (int d = 0; d < 4; d++) for (int n = 0; n < n_nodes; n++) {
+    int64_t R0[2] = { 0, 0 }, N0[2] = { 0, 0 };
+    for (int f = 0; f < F; f++) {
+      const size_t o = (((size_t)d * n_nodes + n) * F + f) * B * 2;
+      int64_t R[2] = { 0, 0 }, N[2] = { 0, 0 };
+      for (int b = 0; b < B; b++) for (int t = 0; t < 2; t++) {
+        if (risk[o + b * 2 + t] < 0) { err = who + "host_risk holds a negative sum"; return FCU_ERR_ARG; }
+        R[t] += risk[o + b * 2 + t]; N[t] += count[o + b * 2 + t];
+      }
+      if (f == 0) { R0[0] = R[0]; R0[1] = R[1]; N0[0] = N[0]; N0[1] = N[1]; }
+      else if (R[0] != R0[0] || R[1] != R0[1] || N[0] != N0[0] || N[1] != N0[1]) {
+        err = who + "the totals of depth " + std::to_string(d) + " node " + std::to_string(n) + " differ between column 0 and column " + std::to_string(f) + " (a histogram of another shape?)";
+        return FCU_ERR_ARG;
+      }
+    }
+  }
+  for (int d = 0; d < 4; d++) for (int n = 0; n < n_nodes; n++) {
+    int64_t R[2] = { 0, 0 }, NT = 0;
+    const size_t o0 = ((size_t)d * n_nodes + n) * F * B * 2;
+    for (int b = 0; b < B; b++) for (int t = 0; t < 2; t++) { R[t] += risk[o0 + b * 2 + t]; NT += count[o0 + b * 2 + t]; }
+    const int64_t whole = R[0] < R[1] ? R[0] : R[1];
+    int64_t best = whole; int bf = -1, bb = 0;
+    for (int f = 0; f < F; f++) {
+      const size_t o = o0 + (size_t)f * B * 2;
+      int64_t L[2] = { 0, 0 }, NL = 0;
+      for (int b = 0; b < B - 1; b++) {
+        L[0] += risk[o + b * 2]; L[1] += risk[o + b * 2 + 1]; NL += (int64_t)count[o + b * 2] + count[o + b * 2 + 1];
+        if (NL < need || NT - NL < need) continue;
+        const int64_t a = L[0] < L[1] ? L[0] : L[1], r0 = R[0] - L[0], r1 = R[1] - L[1], loss = a + (r0 < r1 ? r0 : r1);
+        if (loss < best) { best = loss; bf = f; bb = b; }      /* strictly: ties stay with the smaller f, then the smaller b */
+      }
+    }
+    const int i = n_nodes - 1 + n;
+    tree->feature[d][i] = (int16_t)bf; tree->thr[d][i] = (uint8_t)bb;
+  }
+  return FCU_OK;
 }
 /* fcu_split_match: likewise */
 inline int match_args_check(int n_pics, const fcu_ctu_out *const *dev_out_a, const fcu_ctu_out *const *dev_out_b, const fcu_pic_match *host_matches, std::string &err)

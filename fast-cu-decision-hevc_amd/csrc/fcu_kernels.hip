@@ -25,6 +25,7 @@
 #include "fcu_trace.h"
 #include "fcu_features.h"
 #include "fcu_risk.h"
+#include "fcu_tree.h"
 
 using namespace fcu;
 
@@ -124,6 +125,7 @@ struct fcu_ctx {
   DevBuf hash;                     /* fcu_picture_hash: plane pointers, hash records, per-chunk partials */
   DevBuf score;                    /* fcu_label_score / fcu_trace_maps: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   DevBuf risk;                     /* fcu_risk_train / fcu_risk_predict / fcu_nobf_maps: pointer arrays, the dropped counter, one table slot per workgroup */
+  DevBuf tree;                     /* fcu_tree_keys / fcu_tree_hist / fcu_tree_train: pointer arrays, the tree, the dropped counter, table slots; training: node indices, a level's histograms */
   DevBuf maps;                     /* fcu_decision_maps / fcu_split_match: picture descriptors, picture records, per-CTU records (when the caller gives none) */
   /* WaveFrontSynchro (allocated by the first binder that makes rows chains): wpp_ctl = the words a launch polls (ticket, abort,
    * one progress word per chain), a multiple of 16 bytes, zeroed before every launch; wpp_sync = one slot of WPP_SYNC_BYTES per chain */
@@ -209,6 +211,7 @@ int fcu_abi_sizeof(int which)
   case FCU_ABI_CTU_SCORE: return (int)sizeof(fcu_ctu_score);
   case FCU_ABI_PIC_SCORE: return (int)sizeof(fcu_pic_score);
   case FCU_ABI_RISK_MODEL: return (int)sizeof(fcu_risk_model);
+  case FCU_ABI_KEY_TREE: return (int)sizeof(fcu_key_tree);
   default: return -1;
   }
 }
@@ -243,7 +246,7 @@ void fcu_destroy(fcu_ctx *c)
   hipSetDevice(c->hs.sp.device);
   hipDeviceSynchronize();
   for (hipEvent_t e : c->ev) hipEventDestroy(e);
-  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p); hipFree(c->score.p); hipFree(c->risk.p);
+  hipFree(c->d_chains); hipFree(c->d_scratch); hipFree(c->hist.p); hipFree(c->thr.p); hipFree(c->sao.p); hipFree(c->rep.p); hipFree(c->hash.p); hipFree(c->maps.p); hipFree(c->score.p); hipFree(c->risk.p); hipFree(c->tree.p);
   hipFree(c->wpp_ctl.p); hipFree(c->wpp_sync.p);
   delete c;
 }
@@ -1137,5 +1140,173 @@ int fcu_nobf_maps(fcu_ctx *c, int n_pics, const int16_t *const *dev_obf, uint16_
 }
 
 void fcu_risk_table(const fcu_risk_model *host_model, int min_count, int8_t table[4][FCU_RISK_BINS]) { risk_table(host_model, min_count, table); }
+
+/* the key tree: feat_bins, tree_keys, tree_hist + tree_fold (fcu_tree.h); the split choice is host arithmetic (fcu_host.h) */
+int fcu_feature_edges_check(const float *host_edges, int sets)
+{
+  std::string err;
+  const int rc = tree_edges_check(host_edges, sets, err);
+  return rc == FCU_OK ? FCU_OK : fail(rc, err);
+}
+int fcu_tree_split(const int64_t *host_risk, const uint32_t *host_count, int F, int level, int min_count, fcu_key_tree *tree)
+{
+  std::string err;
+  const int rc = tree_split(host_risk, host_count, F, level, min_count, tree, err);
+  return rc == FCU_OK ? FCU_OK : fail(rc, err);
+}
+
+int fcu_feature_bins(fcu_ctx *c, int n_pics, int sets, const float *dev_features, const float *dev_edges, uint8_t *dev_bins, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_feature_bins: null context");
+  { std::string err; const int rc = feature_bins_args_check(n_pics, sets, dev_features, dev_edges, dev_bins, c->hs.label_count(), err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const TreePlan P = tree_plan(G, TREE_BIN_ROWS);
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  hipLaunchKernelGGL(feat_bins, dim3((unsigned)P.wg_off[4], (unsigned)n_pics), dim3(TREE_THREADS), 0, st, dev_features, dev_edges, dev_bins, G, P, feature_count(sets));
+  HIPCHK(hipGetLastError());
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+/* where the sub-blocks of fcu_ctx::tree lie for a call on n_pics pictures whose deepest histogram level is max_level (-1: none);
+ * train: also the node indices and a level's histograms */
+struct TreeBufs { size_t tr, bins, nodes, tree, drop, slots, keys, risk, count, total; };
+static TreeBufs tree_bufs(const MapsGeom &G, int n_pics, int F, int max_level, bool train)
+{
+  TreeBufs B = {};
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o = up(o + bytes); return at; };
+  B.tr = take(sizeof(void *) * n_pics); B.bins = take(sizeof(void *) * n_pics); B.nodes = take(sizeof(void *) * n_pics);
+  B.tree = take(sizeof(fcu_key_tree)); B.drop = take(sizeof(uint32_t));
+  B.slots = take(max_level < 0 ? 0 : sizeof(TreeSlot) * (size_t)tree_hist_groups(tree_hist_plan(G, n_pics, F, max_level)));
+  B.keys = take(train ? sizeof(uint16_t) * (size_t)n_pics * (size_t)G.lvl_off[4] : 0);
+  B.risk = take(train && max_level >= 0 ? sizeof(int64_t) * (size_t)tree_hist_cells(F, max_level) : 0);
+  B.count = take(train && max_level >= 0 ? sizeof(uint32_t) * (size_t)tree_hist_cells(F, max_level) : 0);
+  B.total = o;
+  return B;
+}
+/* tree_keys for `levels` steps of *host_tree on the device array d_bins of picture pointers (queued; host_tree is copied before
+ * the return of the caller's synchronisation) */
+static int tree_keys_launch(fcu_ctx *c, hipStream_t st, const MapsGeom &G, int n_pics, int F, const TreeBufs &B, const fcu_key_tree *host_tree, int levels, uint16_t *dev_keys)
+{
+  uint8_t *base = (uint8_t *)c->tree.p;
+  HIPCHK(hipMemcpyAsync(base + B.tree, host_tree, sizeof(fcu_key_tree), hipMemcpyHostToDevice, st));
+  const TreePlan P = tree_plan(G, TREE_THREADS);
+  hipLaunchKernelGGL(tree_keys, dim3((unsigned)P.wg_off[4], (unsigned)n_pics), dim3(TREE_THREADS), 0, st, (const uint8_t *const *)(base + B.bins), (const fcu_key_tree *)(base + B.tree), levels, dev_keys, G, P, F);
+  HIPCHK(hipGetLastError());
+  return FCU_OK;
+}
+/* tree_hist + tree_fold of `level` on the device arrays of picture pointers (queued) */
+static int tree_hist_launch(fcu_ctx *c, hipStream_t st, const MapsGeom &G, int n_pics, int F, const TreeBufs &B, int level, bool with_nodes, int64_t *dev_risk, uint32_t *dev_count, int accumulate, Events *ev)
+{
+  uint8_t *base = (uint8_t *)c->tree.p;
+  const TreeHistPlan P = tree_hist_plan(G, n_pics, F, level);
+  TreeSlot *d_slots = (TreeSlot *)(base + B.slots);
+  hipLaunchKernelGGL(tree_hist, dim3((unsigned)tree_hist_groups(P)), dim3(TREE_THREADS), 0, st, (const fcu_cu_trace *const *)(base + B.tr), (const uint8_t *const *)(base + B.bins),
+                     with_nodes ? (const uint16_t *const *)(base + B.nodes) : nullptr, d_slots, G, P);
+  HIPCHK(hipGetLastError());
+  if (ev) HIPCHK(ev->record(1));
+  hipLaunchKernelGGL(tree_fold, dim3((unsigned)((tree_hist_cells(F, level) + 1 + TREE_FOLD_THREADS - 1) / TREE_FOLD_THREADS)), dim3(TREE_FOLD_THREADS), 0, st, d_slots, P, dev_risk, dev_count,
+                     (uint32_t *)(base + B.drop), accumulate);
+  HIPCHK(hipGetLastError());
+  return FCU_OK;
+}
+
+int fcu_tree_keys(fcu_ctx *c, int n_pics, int sets, const uint8_t *dev_bins, const fcu_key_tree *host_tree, int levels, uint16_t *dev_keys, float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_tree_keys: null context");
+  { std::string err; const int rc = tree_keys_args_check(n_pics, sets, dev_bins, host_tree, levels, dev_keys, c->hs.label_count(), err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const int F = feature_count(sets);
+  const TreeBufs B = tree_bufs(G, n_pics, F, -1, false);
+  HIPCHK(c->tree.reserve(B.total, st));
+  std::vector<const uint8_t *> hp((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) hp[i] = dev_bins + (size_t)i * (size_t)G.lvl_off[4] * (size_t)F;
+  HIPCHK(hipMemcpyAsync((uint8_t *)c->tree.p + B.bins, hp.data(), sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2)); HIPCHK(ev.record(0));
+  CHK(tree_keys_launch(c, st, G, n_pics, F, B, host_tree, levels, dev_keys));
+  HIPCHK(ev.record(1));
+  HIPCHK(hipStreamSynchronize(st));                          /* hp and host_tree are done with */
+  if (kernel_ms) ev.ms(kernel_ms, 0, 1);
+  return FCU_OK;
+}
+
+int fcu_tree_hist(fcu_ctx *c, int n_pics, int sets, int level, const fcu_cu_trace *const *dev_trace, const uint8_t *const *dev_bins, const uint16_t *const *dev_nodes,
+                  int64_t *dev_risk, uint32_t *dev_count, int accumulate, uint32_t *host_dropped, float *kernel_ms2, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_tree_hist: null context");
+  { std::string err; const int rc = tree_hist_args_check(n_pics, sets, level, dev_trace, dev_bins, dev_nodes, dev_risk, dev_count, accumulate, c->hs.label_count(), err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const int F = feature_count(sets);
+  const TreeBufs B = tree_bufs(G, n_pics, F, level, false);
+  HIPCHK(c->tree.reserve(B.total, st));
+  uint8_t *base = (uint8_t *)c->tree.p;
+  HIPCHK(hipMemcpyAsync(base + B.tr, dev_trace, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(base + B.bins, dev_bins, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  if (dev_nodes) HIPCHK(hipMemcpyAsync(base + B.nodes, dev_nodes, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  Events ev(st, kernel_ms2 != nullptr);
+  HIPCHK(ev.create(3)); HIPCHK(ev.record(0));
+  CHK(tree_hist_launch(c, st, G, n_pics, F, B, level, dev_nodes != nullptr, dev_risk, dev_count, accumulate, &ev));
+  HIPCHK(ev.record(2));
+  uint32_t dropped = 0;
+  HIPCHK(hipMemcpyAsync(&dropped, base + B.drop, sizeof(dropped), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));                          /* the caller's arrays and `dropped` are done with */
+  if (host_dropped) *host_dropped = dropped;
+  if (kernel_ms2) { ev.ms(&kernel_ms2[0], 0, 1); ev.ms(&kernel_ms2[1], 1, 2); }
+  return FCU_OK;
+}
+
+int fcu_tree_train(fcu_ctx *c, int n_pics, int sets, int levels, int min_count, const fcu_cu_trace *const *dev_trace, const uint8_t *const *dev_bins, fcu_key_tree *host_tree,
+                   float *kernel_ms, void *hip_stream)
+{
+  if (!c) return fail(FCU_ERR_ARG, "fcu_tree_train: null context");
+  { std::string err; const int rc = tree_train_args_check(n_pics, sets, levels, min_count, dev_trace, dev_bins, host_tree, c->hs.label_count(), err); if (rc != FCU_OK) return fail(rc, err); }
+  HIPCHK(hipSetDevice(c->hs.sp.device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const MapsGeom G = maps_geom(c->hs.sp.width, c->hs.sp.height, 0, nullptr);
+  const int F = feature_count(sets);
+  const TreeBufs B = tree_bufs(G, n_pics, F, levels - 1, true);
+  HIPCHK(c->tree.reserve(B.total, st));
+  uint8_t *base = (uint8_t *)c->tree.p;
+  uint16_t *d_keys = (uint16_t *)(base + B.keys);
+  std::vector<const uint16_t *> nodes((size_t)n_pics);
+  for (int i = 0; i < n_pics; i++) nodes[i] = d_keys + (size_t)i * (size_t)G.lvl_off[4];
+  HIPCHK(hipMemcpyAsync(base + B.tr, dev_trace, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(base + B.bins, dev_bins, sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(base + B.nodes, nodes.data(), sizeof(void *) * n_pics, hipMemcpyHostToDevice, st));
+  tree_clear(*host_tree, levels);
+  std::vector<int64_t> h_risk; std::vector<uint32_t> h_count;
+  Events ev(st, kernel_ms != nullptr);
+  HIPCHK(ev.create(2));
+  float total = 0.f;
+  for (int l = 0; l < levels; l++) {
+    const size_t cells = (size_t)tree_hist_cells(F, l);
+    h_risk.resize(cells); h_count.resize(cells);
+    HIPCHK(ev.record(0));
+    if (l > 0) CHK(tree_keys_launch(c, st, G, n_pics, F, B, host_tree, l, d_keys));
+    CHK(tree_hist_launch(c, st, G, n_pics, F, B, l, l > 0, (int64_t *)(base + B.risk), (uint32_t *)(base + B.count), 0, nullptr));
+    HIPCHK(ev.record(1));
+    HIPCHK(hipMemcpyAsync(h_risk.data(), base + B.risk, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_count.data(), base + B.count, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (kernel_ms) { float ms = 0.f; ev.ms(&ms, 0, 1); total += ms; }
+    std::string err;
+    const int rc = tree_split(h_risk.data(), h_count.data(), F, l, min_count, host_tree, err);
+    if (rc != FCU_OK) return fail(rc, err);
+  }
+  HIPCHK(hipStreamSynchronize(st));                          /* (levels 0: the pointer arrays are done with) */
+  if (kernel_ms) *kernel_ms = total;
+  return FCU_OK;
+}
 
 } /* extern "C" */

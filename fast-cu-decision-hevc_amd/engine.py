@@ -185,7 +185,8 @@ EXPORTS = ["fcu_default_frame_params", "fcu_create", "fcu_destroy", "fcu_num_ctu
            "fcu_picture_hash", "fcu_hash_string", "fcu_decision_maps", "fcu_split_match", "fcu_deblock_slices", "fcu_sao_slices",
            "fcu_chain_set_labels", "fcu_label_count", "fcu_labels_from_rasters",
            "fcu_cu_index", "fcu_chain_set_cu_trace", "fcu_label_score", "fcu_trace_maps", "fcu_feature_count", "fcu_feature_maps",
-           "fcu_risk_train", "fcu_risk_predict", "fcu_nobf_maps", "fcu_risk_table"]
+           "fcu_risk_train", "fcu_risk_predict", "fcu_nobf_maps", "fcu_risk_table",
+           "fcu_feature_edges_check", "fcu_feature_bins", "fcu_tree_keys", "fcu_tree_hist", "fcu_tree_split", "fcu_tree_train"]
 MAX_REF = 4                                                # FCU_MAX_REF: reference pictures in list 0
 
 SLICE_I, SLICE_P = 0, 1
@@ -214,6 +215,62 @@ def risk_table(model, min_count=1):
     out = np.zeros((4, RISK_BINS), np.int8)
     load_lib().fcu_risk_table(m.ctypes.data, int(min_count), out.ctypes.data)
     return out
+
+
+TREE_BINS, TREE_MAX_LEVELS, TREE_NODES = 32, 5, 31           # FCU_TREE_BINS, FCU_TREE_MAX_LEVELS, FCU_TREE_NODES
+
+
+class KeyTree(C.Structure):
+    """fcu_key_tree: per depth a complete binary tree in heap order over the binned feature columns (include/fcu.h)"""
+    _fields_ = [("levels", C.c_int32), ("feature", (C.c_int16 * TREE_NODES) * 4), ("thr", (C.c_uint8 * TREE_NODES) * 4)]
+
+    def __init__(self, levels=0):
+        super().__init__()
+        self.levels = levels
+        for d in range(4):
+            for i in range(TREE_NODES):
+                self.feature[d][i] = -1
+
+    def arrays(self):
+        """(levels, feature int16 [4, 31], thr uint8 [4, 31]) as numpy copies"""
+        return int(self.levels), np.array([list(r) for r in self.feature], np.int16), np.array([list(r) for r in self.thr], np.uint8)
+
+
+def tree_hist_shape(n_features, level):
+    """the shape of both histograms of fcu_tree_hist: [depth, node, column, bin, split_won]"""
+    return (4, 1 << level, n_features, TREE_BINS, 2)
+
+
+def tree_split(risk, count, level, tree, min_count=1):
+    """fcu_tree_split: fills the nodes of `level` of `tree` (a KeyTree, changed in place) from host copies of that level's
+    histograms, int64 / uint32 [4, 2^level, F, 32, 2].  Host integer arithmetic of libfcu.so; needs no GPU.  The caller sets
+    tree.levels."""
+    risk, count = np.ascontiguousarray(risk, np.int64), np.ascontiguousarray(count, np.uint32)
+    if risk.ndim != 5 or risk.shape != count.shape or risk.shape != tree_hist_shape(risk.shape[2], level):
+        raise ValueError("tree_split: histograms are [4, 2^level, F, 32, 2]")
+    lib = load_lib()
+    if lib.fcu_tree_split(risk.ctypes.data, count.ctypes.data, risk.shape[2], int(level), int(min_count), C.byref(tree)) != 0:
+        raise FcuError("fcu_tree_split: " + lib.fcu_last_error().decode())
+    return tree
+
+
+def feature_edges(X, width, height):
+    """The driver's default edges for feature_bins: X = the float32 tensor [n, NL, F] of feature_maps for pictures of
+    width x height.  Per (level, column) the rows of that level -- of all n pictures -- are sorted with torch on X's device and
+    the values at ranks round(k * rows / 32), k = 1..31, are taken: float32 [4, F, 31] on that device.  A constant column gives
+    equal edges.  Not part of the ABI: any finite, non-decreasing edges do."""
+    import torch
+    shapes = map_level_shapes(width, height)
+    assert X.dim() == 3 and X.shape[1] == sum(a * b for a, b in shapes), "feature_edges: [n, NL, F] of feature_maps"
+    out, o = [], 0
+    for bh, bw in shapes:
+        rows = X[:, o:o + bh * bw, :].reshape(-1, X.shape[2])
+        o += bh * bw
+        s = torch.sort(rows, dim=0).values
+        n = s.shape[0]
+        rank = torch.tensor([min(n - 1, int(round(k * n / TREE_BINS))) for k in range(1, TREE_BINS)], device=X.device)
+        out.append(s.index_select(0, rank).t())
+    return torch.stack(out).contiguous().to(torch.float32)
 
 
 # FCU_FEATSET_*: the feature sets of fcu_feature_maps, in column order, and the names of their columns (include/fcu.h):
@@ -348,6 +405,12 @@ def load_lib():
     lib.fcu_risk_train.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_risk_predict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_nobf_maps.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fcu_feature_edges_check.argtypes = [C.c_void_p, C.c_int]
+    lib.fcu_feature_bins.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_tree_keys.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_tree_hist.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_void_p]
+    lib.fcu_tree_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.fcu_tree_train.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
     lib.fcu_risk_table.restype = None
     lib.fcu_risk_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     _lib = lib
@@ -897,6 +960,96 @@ class CuEngine:
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._chk(self.lib.fcu_nobf_maps(self.h, n, ptrs, out.data_ptr(), s), "fcu_nobf_maps")
         return out
+
+    # -- the key tree: risk-table keys learnt from the feature maps (include/fcu.h)
+    def _bins_ptrs(self, bins, F, who):
+        n = len(bins)
+        rows = [bins[i] for i in range(n)]
+        for t in rows:
+            assert t.is_cuda and t.dtype == self.torch.uint8 and t.is_contiguous() and t.numel() == self.label_count() * F, who + ": uint8 [NL, F] bins on the device"
+        return (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in rows]), rows
+
+    def feature_bins(self, features, edges, sets=("tmv", "soc"), out=None, timed=False, stream=None):
+        """The columns of feature_maps quantised to 32 bins (fcu_feature_bins): features float32 [n, NL, F] on the device; edges
+        float32 [4, F, 31] -- a device tensor (feature_edges; read as it is) or a host array, which is checked to be finite and
+        non-decreasing (fcu_feature_edges_check) and copied.  Returns the uint8 device tensor [n, NL, F] (out: a contiguous uint8
+        tensor of that many bytes to write instead, at any byte offset).  timed=True: (tensor, kernel ms)."""
+        torch = self.torch
+        mask, names = feature_sets(sets)
+        F, NL = sum(FEATURE_COUNTS[k] for k in names), self.label_count()
+        assert features.is_cuda and features.dtype == torch.float32 and features.is_contiguous() and features.dim() == 3 and tuple(features.shape[1:]) == (NL, F), "feature_bins: float32 [n, NL, F] on the device"
+        n = features.shape[0]
+        if not torch.is_tensor(edges):
+            e = np.ascontiguousarray(edges, np.float32)
+            assert e.shape == (4, F, TREE_BINS - 1), "feature_bins: edges are [4, F, 31]"
+            self._chk(self.lib.fcu_feature_edges_check(e.ctypes.data, mask), "fcu_feature_edges_check")
+            edges = torch.tensor(e, device=features.device)
+        assert edges.is_cuda and edges.dtype == torch.float32 and edges.is_contiguous() and tuple(edges.shape) == (4, F, TREE_BINS - 1), "feature_bins: edges are float32 [4, F, 31]"
+        if out is None:
+            out = torch.empty((n, NL, F), dtype=torch.uint8, device=features.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * NL * F, "feature_bins: out is uint8 [n, NL, F]"
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_feature_bins(self.h, n, mask, features.data_ptr(), edges.data_ptr(), out.data_ptr(), C.byref(ms) if timed else None, s), "fcu_feature_bins")
+        return (out, float(ms.value)) if timed else out
+
+    def tree_keys(self, bins, tree, levels=None, sets=("tmv", "soc"), timed=False, stream=None):
+        """The key of every block (fcu_tree_keys): bins the uint8 device tensor [n, NL, F] of feature_bins, tree a KeyTree; levels
+        (default tree.levels) below tree.levels gives the node-in-level index training needs.  Returns the uint16 device tensor
+        [n, NL] that risk_train / risk_predict take as keys.  timed=True: (tensor, kernel ms)."""
+        torch = self.torch
+        mask, names = feature_sets(sets)
+        F, NL = sum(FEATURE_COUNTS[k] for k in names), self.label_count()
+        assert bins.is_cuda and bins.dtype == torch.uint8 and bins.is_contiguous() and bins.numel() % (NL * F) == 0 and bins.numel() > 0, "tree_keys: uint8 [n, NL, F] on the device"
+        n = bins.numel() // (NL * F)
+        out = torch.empty((n, NL), dtype=torch.uint16, device=bins.device)
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_tree_keys(self.h, n, mask, bins.data_ptr(), C.byref(tree), int(tree.levels if levels is None else levels), out.data_ptr(), C.byref(ms) if timed else None, s), "fcu_tree_keys")
+        return (out, float(ms.value)) if timed else out
+
+    def tree_hist(self, traces, bins, level, nodes=None, sets=("tmv", "soc"), hist=None, accumulate=False, timed=False, stream=None):
+        """The histograms a level of the tree is chosen from (fcu_tree_hist).  traces: as risk_train; bins: a uint8 tensor
+        [n, NL, F] or a list of [NL, F] tensors; nodes: uint16 [n, NL] (or a list) from tree_keys(levels=level), None at level 0.
+        hist: (risk int64, count uint32) device tensors [4, 2^level, F, 32, 2] to write (accumulate=False: overwritten, nothing to
+        clear) or to add to; None: new ones.  Returns (risk, count, dropped) -- dropped = samples whose node was >= 2^level.
+        timed=True: also the durations (ms) of the two kernels."""
+        torch = self.torch
+        mask, names = feature_sets(sets)
+        F = sum(FEATURE_COUNTS[k] for k in names)
+        n = len(traces)
+        assert len(bins) == n and (nodes is None or len(nodes) == n)
+        tp = self._trace_ptrs(traces, "tree_hist")
+        bp, keep_b = self._bins_ptrs(bins, F, "tree_hist")
+        np_, keep_n = self._key_ptrs(nodes, "tree_hist") if nodes is not None else (None, None)
+        shape = tree_hist_shape(F, level)
+        if hist is None:
+            assert not accumulate, "tree_hist: accumulate=True adds to histograms"
+            dev = torch.device("cuda", self.device)
+            hist = (torch.empty(shape, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.uint32, device=dev))
+        risk, count = hist
+        assert risk.is_cuda and risk.dtype == torch.int64 and risk.is_contiguous() and tuple(risk.shape) == shape and count.is_cuda and count.dtype == torch.uint32 and count.is_contiguous() and tuple(count.shape) == shape, "tree_hist: int64 / uint32 [4, 2^level, F, 32, 2] on the device"
+        dropped = C.c_uint32(0)
+        ms = (C.c_float * 2)() if timed else None
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_tree_hist(self.h, n, mask, int(level), tp, bp, np_, risk.data_ptr(), count.data_ptr(), 1 if accumulate else 0, C.byref(dropped), ms, s), "fcu_tree_hist")
+        return (risk, count, int(dropped.value), (ms[0], ms[1])) if timed else (risk, count, int(dropped.value))
+
+    def tree_train(self, traces, bins, levels, min_count=1, sets=("tmv", "soc"), timed=False, stream=None):
+        """Trains a KeyTree of `levels` levels level by level (fcu_tree_train): keys, histograms, the copy of a level's histograms
+        to the host, the split choice.  traces / bins as tree_hist.  Synchronous.  Returns the KeyTree; timed=True: (tree, the
+        kernels' durations added up in ms)."""
+        mask, names = feature_sets(sets)
+        F = sum(FEATURE_COUNTS[k] for k in names)
+        n = len(traces)
+        assert len(bins) == n
+        tp = self._trace_ptrs(traces, "tree_train")
+        bp, keep_b = self._bins_ptrs(bins, F, "tree_train")
+        tree = KeyTree()
+        ms = C.c_float(0)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._chk(self.lib.fcu_tree_train(self.h, n, mask, int(levels), int(min_count), tp, bp, C.byref(tree), C.byref(ms) if timed else None, s), "fcu_tree_train")
+        return (tree, float(ms.value)) if timed else tree
 
     # -- getTMVFeature / FormFeatureVector(SOC)
     def feature_maps(self, lumas, sets=("tmv", "soc"), yc=None, timed=False, stream=None):

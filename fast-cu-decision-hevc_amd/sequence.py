@@ -143,14 +143,36 @@ class SequenceDecider:
         CuEngine.nobf_maps(obf), or key(poc, planes, obf, n_obf) -> uint16 device tensor [NL].  Every Verifying and Testing
         picture gets CuEngine.risk_predict on its own keys and the labels bound to all its chains: the Verifying counters,
         fcu_decision_switch and the per-depth switches work on them unchanged.  The result dicts of such pictures carry `labels`;
-        `risk_model` is the model's device tensor (None before the first Training group)."""
+        `risk_model` is the model's device tensor (None before the first Training group).
+        risk={"tree": {"levels": T, "sets": ("tmv", "soc"), "min_count": 1}} (not together with key): the keys are the leaves of a
+        key tree over the binned feature maps (include/fcu.h).  The driver keeps the traces and features of the period's Training
+        pictures; when the schedule leaves Training it forms the default edges (engine.feature_edges), the bins, the tree
+        (CuEngine.tree_train), its keys and one CuEngine.risk_train over all of them; every Verifying / Testing picture gets
+        feature_maps, feature_bins, tree_keys and risk_predict.  `key_tree` and `tree_edges` hold the tree and the edges."""
         if risk is None or risk is False:
             self.risk = None
         else:
-            if risk is not True and (not isinstance(risk, dict) or set(risk) - {"min_count", "key"}):
-                raise ValueError("SequenceDecider: risk is None, True or a dict with min_count / key")
-            self.risk = {"min_count": 1, "key": None}
+            if risk is not True and (not isinstance(risk, dict) or set(risk) - {"min_count", "key", "tree"}):
+                raise ValueError("SequenceDecider: risk is None, True or a dict with min_count / key / tree")
+            self.risk = {"min_count": 1, "key": None, "tree": None}
             self.risk.update({} if risk is True else risk)
+            if self.risk["tree"] is not None:
+                tr = self.risk["tree"]
+                if not isinstance(tr, dict) or "levels" not in tr or set(tr) - {"levels", "sets", "min_count"}:
+                    raise ValueError("SequenceDecider: risk tree is a dict with levels and, optionally, sets / min_count")
+                if self.risk["key"] is not None:
+                    raise ValueError("SequenceDecider: risk tree and risk key both name the keys of the risk table; give one")
+                tr = dict({"sets": ("tmv", "soc"), "min_count": 1}, **tr)
+                for k in ("levels", "min_count"):
+                    if not isinstance(tr[k], (int, np.integer)) or isinstance(tr[k], bool) or tr[k] < 0 or (k == "levels" and tr[k] > _engine.TREE_MAX_LEVELS):
+                        raise ValueError("SequenceDecider: risk tree levels is 0 .. 5 and min_count a non-negative integer")
+                try:
+                    tr["sets"] = _engine.feature_sets(tr["sets"])[1]
+                    if not tr["sets"]:
+                        raise ValueError("no feature set")
+                except ValueError as e:
+                    raise ValueError("SequenceDecider: risk tree sets: %s" % e)
+                self.risk["tree"] = tr
             mc = self.risk["min_count"]
             if not isinstance(mc, (int, np.integer)) or isinstance(mc, bool) or mc < 0:
                 raise ValueError("SequenceDecider: risk min_count is a non-negative integer")
@@ -161,6 +183,7 @@ class SequenceDecider:
             if labels is not None:
                 raise ValueError("SequenceDecider: risk and labels both name the model of the Verifying / Testing pictures; give one")
         self.risk_model = None
+        self.key_tree, self.tree_edges, self._tree_train = None, None, []      # risk tree: the tree, its edges, (trace, features) of the period's Training pictures
         self.do_report = report
         self.features = None if features is None or features is False else _engine.feature_sets(("tmv", "soc") if features is True else features)[1]
         if labels is not None and not callable(labels):
@@ -217,9 +240,11 @@ class SequenceDecider:
                     eng.set_decision(first + k, state, obf, sk, te)
                 lab = self.labels(poc, eng.org_planes(first), obf) if self.labels is not None else None
                 if self.risk is not None:
+                    if self._tree_train:                       # the schedule has left Training: edges, tree, keys, one risk_train
+                        self._tree_fit()
                     if self.risk_model is None:
                         raise ValueError("SequenceDecider: risk has no model yet: the schedule needs at least one Training picture per period")
-                    lab = eng.risk_predict(self._risk_keys(poc, first, obf)[None], self.risk_model, self.risk["min_count"])[0]
+                    lab = eng.risk_predict(self._risk_keys(poc, first, obf, yc)[None], self.risk_model, self.risk["min_count"])[0]
                 if lab is not None:                            # labels are per picture: every chain of it takes the one array
                     eng.set_labels(range(first, first + n_sl), lab)
             pics.append({"poc": poc, "state": state, "sw_skip": sk, "sw_term": te, "out": out, "rec": rec, "first": first})
@@ -228,7 +253,7 @@ class SequenceDecider:
                 for k in range(1, n_sl):
                     eng.enable_cu_trace(first + k, tr)
                 pics[-1]["cu_trace"] = tr
-                if self.risk is not None:                      # the keys of a Training picture: its own pre-pass; the chains are not given the map
+                if self.risk is not None and self.risk["tree"] is None:      # the keys of a Training picture: its own pre-pass; the chains are not given the map
                     pics[-1]["risk_keys"] = self._risk_keys(poc, first, eng.obf_prepass(eng.org_planes(first)[0])[0][0].contiguous())
             if state != TRAINING and lab is not None:
                 pics[-1]["labels"] = lab
@@ -238,7 +263,12 @@ class SequenceDecider:
                 pics[-1]["yc"] = yc[0] if yc is not None else eng.obf_prepass(eng.org_planes(first)[0])[1][0]
         eng.compress_pictures(0, len(yuvs), self.layout)
         nb = _engine.CTU_OUT_BYTES
-        if self.risk is not None and pics[0]["state"] == TRAINING:      # the pictures of a group share their state
+        if self.risk is not None and self.risk["tree"] is not None and pics[0]["state"] == TRAINING:
+            if pics[0]["poc"] % self.schedule.period == 0:     # a new period: its own tree and model
+                self._tree_train = []
+            for p in pics:                                     # kept until the schedule leaves Training (_tree_fit)
+                self._tree_train.append((p["cu_trace"], self._tree_features(p["first"])[0].clone()))
+        elif self.risk is not None and pics[0]["state"] == TRAINING:      # the pictures of a group share their state
             first_group = pics[0]["poc"] % self.schedule.period == 0
             self.risk_model, _ = eng.risk_train(pics, [p.pop("risk_keys") for p in pics], model=None if first_group else self.risk_model, accumulate=not first_group)
         for p in pics:
@@ -269,8 +299,30 @@ class SequenceDecider:
         self.poc += len(yuvs)
         return pics
 
-    def _risk_keys(self, poc, first, obf):
-        """the uint16 [NL] key array of a picture: its N_OBF map, or what the caller's key function makes of it"""
+    def _tree_features(self, first, yc=None):
+        """float32 [1, NL, F] of the picture bound to chain `first`, in the tree's feature sets (yc: its pre-pass thresholds, formed here when None)"""
+        sets = self.risk["tree"]["sets"]
+        if "soc" in sets and yc is None:
+            yc = self.eng.obf_prepass(self.eng.org_planes(first)[0])[1]
+        return self.eng.feature_maps([self.eng.org_planes(first)[0]], sets=sets, yc=yc[:1] if "soc" in sets else None)
+
+    def _tree_fit(self):
+        """what leaving Training does with risk tree: default edges from the Training pictures' features, their bins, the tree, its
+        keys, and one risk_train over all of them"""
+        eng, opt = self.eng, self.risk["tree"]
+        traces = [t for t, _ in self._tree_train]
+        X = self.eng.torch.stack([x for _, x in self._tree_train])
+        self._tree_train = []
+        self.tree_edges = _engine.feature_edges(X, self.width, self.height)
+        bins = eng.feature_bins(X, self.tree_edges, sets=opt["sets"])
+        self.key_tree = eng.tree_train(traces, bins, opt["levels"], opt["min_count"], sets=opt["sets"])
+        self.risk_model, _ = eng.risk_train(traces, eng.tree_keys(bins, self.key_tree, sets=opt["sets"]))
+
+    def _risk_keys(self, poc, first, obf, yc=None):
+        """the uint16 [NL] key array of a picture: its N_OBF map, what the caller's key function makes of it, or the tree's keys"""
+        if self.risk["tree"] is not None:
+            sets = self.risk["tree"]["sets"]
+            return self.eng.tree_keys(self.eng.feature_bins(self._tree_features(first, yc), self.tree_edges, sets=sets), self.key_tree, sets=sets)[0]
         n_obf = self.eng.nobf_maps(obf)[0]
         if self.risk["key"] is None:
             return n_obf

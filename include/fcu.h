@@ -56,6 +56,10 @@
  *     label, J0, J1 per CU (tools_YS.cpp:304-318,     per CTU), fcu_trace_maps (the trace as label / J0 / J1 maps aligned with N_OBF),
  *      968-986; TEncCu.cpp:1450-1451,1489-1497)       fcu_label_score (countTFPN + countRDLoss of any label array against a trace,
  *                                                    without deciding the picture again), fcu_cu_index
+ *   the fork's tree model type RTS_OpenCV           fcu_feature_bins (feature maps -> 32 bins per column), fcu_tree_train / fcu_tree_hist /
+ *     (CvRTrees_model, globals_YS.h:124: OpenCV's     fcu_tree_split (a small tree per depth over the binned columns, from integer
+ *      random trees, external)                        histograms of the trace's quantised loss), fcu_tree_keys (its leaf index as
+ *                                                    the key of the risk table): this library's definition, not OpenCV's
  *   m_pppcRDSbacCoder[0][CI_CURR_BEST] state      fcu_get_ctx_state
  *     (TEncSlice.cpp:1417,1477)
  *
@@ -736,6 +740,75 @@ int  fcu_risk_predict(fcu_ctx *c, int n_pics, const uint16_t *const *dev_keys, c
 int  fcu_nobf_maps(fcu_ctx *c, int n_pics, const int16_t *const *dev_obf, uint16_t *dev_nobf, void *hip_stream);
 void fcu_risk_table(const fcu_risk_model *host_model, int min_count, int8_t table[4][FCU_RISK_BINS]);
 
+/* ---- key tree: risk-table keys learnt from the feature maps.  One small decision tree per CU depth over the quantised columns
+ * of fcu_feature_maps; its leaf index is the uint16 key of fcu_risk_train / fcu_risk_predict.  The fork's tree model type is
+ * RTS_OpenCV (CvRTrees_model, globals_YS.h:124): OpenCV's random trees, an external library.  Nothing below is the fork's: bins,
+ * tree, histograms and the split rule are this library's, as the training rule of the risk table is.  Every quantity is an
+ * integer, every result is the same bytes in any order of evaluation.
+ * F = fcu_feature_count(sets); rows, NL, off(d), BW(d) and the block addressing are those of the label maps.
+ *   bins     edges is float32 [4][F][FCU_TREE_BINS - 1]: per (level d of the NL layout, column) 31 finite, non-decreasing values.
+ *            The bin of x is the number of edges e with e <= x, 0..31; NaN compares false and gives bin 0.  Equal edges are
+ *            allowed and leave bins unreachable.  A row of level d uses edges[d].
+ *   tree     fcu_key_tree: per depth d a complete binary tree in heap order (node i has children 2 i + 1 and 2 i + 2), `levels`
+ *            (0..5) deep, so at most 32 leaves.  feature[d][i] is the column node i splits on, or -1 for a node that is not
+ *            split; thr[d][i] is 0..30.  The walk of a row of level d starts at node 0 and takes exactly `levels` steps: at a
+ *            split node it goes right iff bin[feature] > thr, at an unsplit node left.  key = the heap index reached -
+ *            (2^levels - 1), in [0, 2^levels).  levels 0: key 0 everywhere.
+ *   hist     sample and quantised loss q are exactly those of fcu_risk_train (valid, split_tried and whole_tried all set;
+ *            q = floor(|j0 - j1| * 256) clamped to 2^40 - 1), one function for both; the record of CTU a, depth d, z-index z is the
+ *            row fcu_risk_train reads its key from.  risk is int64 [4][2^level][F][32][2], count uint32 of the same shape: cell
+ *            [d][n][f][b][t] = the sum of q, respectively the number, over the samples of depth d in node n whose bin of column f
+ *            is b and whose split_won is t.  Capacity as for the risk model: 2^23 samples per cell, 2^22 blocks per call.
+ *   split    for depth d and node n with total risks R[t]: L[t](f, b) = the cell risks of column f summed over bins <= b;
+ *            loss(f, b) = min(L[0], L[1]) + min(R[0] - L[0], R[1] - L[1]) -- what the best label per child loses, the quantity
+ *            the risk table's rule minimises.  Candidates: b in 0..30 with at least max(1, min_count) samples in both children.
+ *            The smallest loss wins, ties go to the smallest f, then the smallest b; the node is split only if that loss is
+ *            strictly below min(R[0], R[1]), else feature = -1 (and thr = 0).
+ *
+ * fcu_feature_edges_check: FCU_OK for a host copy of edges ([4][F][31]) whose rows are finite and non-decreasing, else FCU_ERR_ARG
+ * with the row named.  Edges formed on the device are the caller's to get right; fcu_feature_bins reads them as they are.
+ * fcu_feature_bins: dev_features float32 [n_pics][NL][F] (4-byte aligned) -> dev_bins uint8 [n_pics][NL][F], which may start at any
+ * byte.  One kernel, a workgroup inside one level with that level's edges in LDS; every output byte is written by exactly one
+ * thread.  The bin is found by a 5-step search over the row of edges, which equals the count above for non-decreasing edges.
+ * fcu_tree_keys: dev_bins as fcu_feature_bins wrote it -> dev_keys uint16 [n_pics][NL] at any even byte.  levels <= tree->levels:
+ * a smaller value walks only that many steps and gives the node-in-level index that training needs.  One kernel, one thread per
+ * block; a block the picture edge cuts walks its zero row like any other.
+ * fcu_tree_hist: the histograms of `level` (0..4).  dev_trace / dev_bins: host arrays of n_pics device pointers (a picture's trace
+ * and its uint8 [NL][F] bins); dev_nodes: host array of n_pics device pointers to uint16 [NL], the output of
+ * fcu_tree_keys(levels = level), may be NULL at level 0 (node 0 everywhere).  accumulate 0 overwrites every cell -- the caller
+ * clears nothing --, accumulate 1 adds: A then B equals [A, B].  A sample whose node index is >= 2^level is dropped and counted
+ * (once, not per column) in host_dropped[0] (may be NULL).  Two kernels as fcu_risk_train: workgroups add into LDS tables of their
+ * own (integer LDS adds) and store them to slots of a context buffer, a second kernel folds the slots, one thread per cell.  No
+ * global atomics: a repeated call gives identical bytes.  kernel_ms2 (may be NULL) receives the two durations.
+ * fcu_tree_split: pure host integer arithmetic, needs no GPU: fills the nodes of `level` from a host copy of that level's
+ * histograms and leaves the rest of the tree alone (the caller sets tree->levels).  The totals of a node are the same whichever
+ * column they are summed over: FCU_ERR_ARG when they are not (a histogram of another shape, F or level).
+ * fcu_tree_train: for each level l < levels: keys of l levels, histograms, copy to the host (at most 7.2 MB), split.  Uses
+ * buffers of the context, synchronous as fcu_obf_prepass; pictures, features and traces stay on the device.  host_tree is
+ * overwritten: levels, every node (-1 / 0 below the trained levels).  kernel_ms (may be NULL): the kernels' durations added up.
+ * FCU_ERR_ARG, with the argument named in fcu_last_error(): n_pics < 1; a bad sets, level or levels; NULL arrays or entries;
+ * misaligned dev_features / dev_keys / dev_nodes / dev_risk / dev_count; a tree whose levels, features or thresholds are out of
+ * range; n_pics * NL > 2^22.  No CPU fallback. */
+#define FCU_TREE_BINS 32
+#define FCU_TREE_MAX_LEVELS 5
+#define FCU_TREE_NODES 31            /* internal nodes of a depth's tree, heap order */
+typedef struct fcu_key_tree {        /* 376 B, no implicit padding (already a multiple of 8) */
+  int32_t levels;                        /* 0..FCU_TREE_MAX_LEVELS */
+  int16_t feature[4][FCU_TREE_NODES];    /* [depth][node]: column, or -1 for a node that is not split */
+  uint8_t thr[4][FCU_TREE_NODES];        /* right iff bin[feature] > thr; 0..30 */
+} fcu_key_tree;
+int  fcu_feature_edges_check(const float *host_edges, int sets);
+int  fcu_feature_bins(fcu_ctx *c, int n_pics, int sets, const float *dev_features, const float *dev_edges, uint8_t *dev_bins,
+                      float *kernel_ms, void *hip_stream);
+int  fcu_tree_keys(fcu_ctx *c, int n_pics, int sets, const uint8_t *dev_bins, const fcu_key_tree *host_tree, int levels,
+                   uint16_t *dev_keys, float *kernel_ms, void *hip_stream);
+int  fcu_tree_hist(fcu_ctx *c, int n_pics, int sets, int level, const fcu_cu_trace *const *dev_trace, const uint8_t *const *dev_bins,
+                   const uint16_t *const *dev_nodes, int64_t *dev_risk, uint32_t *dev_count, int accumulate, uint32_t *host_dropped,
+                   float *kernel_ms2, void *hip_stream);
+int  fcu_tree_split(const int64_t *host_risk, const uint32_t *host_count, int F, int level, int min_count, fcu_key_tree *tree);
+int  fcu_tree_train(fcu_ctx *c, int n_pics, int sets, int levels, int min_count, const fcu_cu_trace *const *dev_trace,
+                    const uint8_t *const *dev_bins, fcu_key_tree *host_tree, float *kernel_ms, void *hip_stream);
+
 /* ---- per-PU record of the luma search (BASELINE configs[1]: intra-luma RDO, TEncSearch::estIntraPredLumaQT over the 35
  * modes at all depths).  Exhaustive RDO visits every PU of the five layers of a CTU -- 1 + 4 + 16 + 64 PUs of 2Nx2N CUs at
  * depth 0..3 and 256 PUs of NxN CUs at depth 3 = 341 -- and estIntraPredLumaQT (TEncSearch.cpp:2178-2655) leaves per PU: the
@@ -772,7 +845,7 @@ const char *fcu_build_info(void);
 enum { FCU_ABI_CTU_OUT = 0, FCU_ABI_SEQ_PARAMS = 1, FCU_ABI_FRAME_PARAMS = 2, FCU_ABI_DECISION_PARAMS = 3, FCU_ABI_VERIFY_COUNTS = 4,
        FCU_ABI_SAO_CTU = 5, FCU_ABI_SAO_PARAMS = 6, FCU_ABI_PU_TRACE = 7, FCU_ABI_PIC_REPORT = 8, FCU_ABI_CTU_REPORT = 9,
        FCU_ABI_PIC_HASH = 10, FCU_ABI_CTU_MATCH = 11, FCU_ABI_PIC_MATCH = 12, FCU_ABI_CU_TRACE = 13, FCU_ABI_CTU_SCORE = 14,
-       FCU_ABI_PIC_SCORE = 15, /* 16 is not assigned and stays unknown */ FCU_ABI_RISK_MODEL = 17 };
+       FCU_ABI_PIC_SCORE = 15, /* 16 is not assigned and stays unknown */ FCU_ABI_RISK_MODEL = 17, FCU_ABI_KEY_TREE = 18 };
 int  fcu_abi_sizeof(int which);
 
 #ifdef __cplusplus

@@ -37,7 +37,7 @@ on the chosen tree -- and `trace_poc`, the POCs of those pictures.
 of `trace_label` / `j0` / `j1` of --cu-trace for the picture of the same POC: the arrays line up row for row.
 --risk (with --fast) runs the cycle on the risk-table model instead of the Naive label: the Training pictures are decided with a CU
 trace, the model is trained on the device from their traces and N_OBF maps (fcu_risk_train) and predicts the split labels of every
-Verifying and Testing picture (fcu_risk_predict); --risk-min-count N leaves a bin with fewer than N training samples without a
+Verifying and Testing picture (fcu_risk_predict); --risk-tree LEVELS keys the table by the leaves of a key tree over the binned feature maps (fcu_tree_train) instead of N_OBF; --risk-min-count N leaves a bin with fewer than N training samples without a
 prediction (default 1; 0 is the fork's rule on every bin).
 """
 import argparse
@@ -81,8 +81,11 @@ def main():
     ap.add_argument("--features", metavar="FILE.npz", help="save the TMV + SOC features of every block of every picture (features [pictures, NL, 146], feature_names, features_poc); "
                                                            "with --cu-trace the arrays line up row for row: row r of `features` of a picture is the block of element r of trace_label / j0 / j1 of the same POC")
     ap.add_argument("--risk", action="store_true", help="with --fast: predict the split labels of the Verifying / Testing pictures with the risk-table model trained on the Training pictures, all on the device")
+    ap.add_argument("--risk-tree", type=int, default=None, metavar="LEVELS", help="with --risk: key the risk table by the leaves of a key tree of LEVELS (0..5) levels trained on the binned feature maps of the Training pictures, in the place of N_OBF")
     ap.add_argument("--risk-min-count", type=int, default=None, metavar="N", help="with --risk: a bin with fewer than N training samples gives no prediction (default 1)")
     args = ap.parse_args()
+    if args.risk_tree is not None and not args.risk:
+        ap.error("--risk-tree needs --risk")
     if args.risk_min_count is not None and not args.risk:
         ap.error("--risk-min-count needs --risk")
     tiles = None
@@ -98,7 +101,7 @@ def main():
     slice_ctus = (args.width + 63) // 64 if args.row_slices else (args.slice_ctus or None)
     try:                                                       # the rules of these combinations: PictureLayout
         dec = seq.SequenceDecider(args.width, args.height, args.qp, slice_ctus=slice_ctus, fast=args.fast, deblock=not args.no_deblock, in_flight=args.in_flight, wpp=args.wpp, slice_rows=args.slice_rows, tiles=tiles, lf_cross_tiles=args.lf_cross_tiles, lf_cross_slices=args.lf_cross_slices, report=args.report, pic_hash=args.hash, maps=True if args.maps else None, cu_trace=bool(args.cu_trace), features=True if args.features else None,
-                                  risk=({"min_count": 1 if args.risk_min_count is None else args.risk_min_count} if args.risk else None),
+                                  risk=(dict({"min_count": 1 if args.risk_min_count is None else args.risk_min_count}, **({"tree": {"levels": args.risk_tree}} if args.risk_tree is not None else {})) if args.risk else None),
                                   schedule=seq.FastDecisionSchedule(args.period, args.training, args.verifying))
     except ValueError as e:
         ap.error(str(e))
