@@ -165,6 +165,9 @@ template <class T> __device__ inline T fcu_uni(T v)
 #elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 3   /* rdoq_wave variant: every slot but 10 (the CTU total) belongs to the sub-timers of rdoq_wave (FCU_WTOC) */
 #define FCU_TOC(E_, v, idx) do { if ((idx) == 10 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
+#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 4   /* level-choice variant: slots 2, 8 and 10 keep their sections and 13 (chroma_rdoq) moves to 3; the others belong to the coefficient loop of rdoq<0> (FCU_LV_*) */
+#define FCU_TOC(E_, v, idx) do { if (((idx) == 2 || (idx) == 8 || (idx) == 10 || (idx) == 13) && threadIdx.x == 0) (E_).C->prof[(idx) == 13 ? 3 : (idx)] += (unsigned long long)(clock64() - v); } while (0)
+#define FCU_COUNT(E_, idx, n) do { } while (0)
 #elif defined(FCU_PROFILE_RDOQ) || defined(FCU_PROFILE_DEPTH)   /* slots 11..15 belong to the sub-timers inside the serial RDOQ (FCU_PROFILE_DEPTH: 11..14 to the time spent at CU depth 0..3 without its sub-CUs) in these variants */
 #define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
@@ -230,7 +233,7 @@ __shared__ HotTables g_hot;
 #if defined(FCU_PROFILE_RQT) && !defined(FCU_EMU)     /* lane 0 of the lane-private RDOQ (the luma variant of an inter TU): slots 11..15 */
 #define FCU_RTIC(v) long long v = clock64()
 #define FCU_RTOC(P_, v, idx) do { if (!SER && threadIdx.x == 0) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
-#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) != 3 && !defined(FCU_EMU)      /* -DFCU_PROFILE_RDOQ: the serial form; -DFCU_PROFILE_RDOQ=2: lane 0 of the lane-private form (rdoq<0>) */
+#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) != 3 && (FCU_PROFILE_RDOQ + 0) != 4 && !defined(FCU_EMU)      /* -DFCU_PROFILE_RDOQ: the serial form; -DFCU_PROFILE_RDOQ=2: lane 0 of the lane-private form (rdoq<0>) */
 #define FCU_RTIC(v) long long v = clock64()
 #define FCU_RTOC(P_, v, idx) do { if ((FCU_PROFILE_RDOQ + 0) == 2 ? (!SER && threadIdx.x == 0) : SER) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
 #else
@@ -247,6 +250,37 @@ __shared__ HotTables g_hot;
 #else
 #define FCU_WTIC(v) do { } while (0)
 #define FCU_WTOC(P_, v, t, log2) do { } while (0)
+#endif
+/* -DFCU_PROFILE -DFCU_PROFILE_RDOQ=4: the coefficient loop of rdoq<0> on lane 0, by kind of iteration.  The ticks between two
+ * iteration tops go to the kind of the iteration they follow: 1 = no lane of the batch has a candidate level (uiMaxAbsLevel 0
+ * on every active lane), 2 = at least one lane takes the level choice; 0 = the head and tail of a coefficient group.  Inside the
+ * level choice, when lane 0 itself takes it: the level choice (xGetCodedLevel), the rates of rateIncUp / rateIncDown, and the
+ * record store with the c1 / c2 / Rice update.  Sums stay in registers and reach the chain once per call: slots 0, 11, 12 =
+ * group / short / long iterations and 13 = level choice, each ticks + (count << 40); 14, 15 = rates, store + update; 1 = the
+ * call up to the end of the walk + (calls << 40).  tests/prof_run_rdoq_level.py prints them. */
+#if defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 4 && !defined(FCU_EMU)
+struct LvProf { long long t0, t, ts; unsigned long long grp, sht, lng, s0, s1, s2; unsigned n_grp, n_sht, n_lng, n_own; int kind; };
+#define FCU_LV_BEGIN(L_) LvProf L_ = { }; L_.t0 = L_.t = clock64()
+#define FCU_LV_TOP(L_, next) do { if (SER) break; const long long n_ = clock64(); const unsigned long long d_ = (unsigned long long)(n_ - L_.t); \
+    if (L_.kind == 0) { L_.grp += d_; L_.n_grp++; } else if (L_.kind == 1) { L_.sht += d_; L_.n_sht++; } else { L_.lng += d_; L_.n_lng++; } \
+    L_.t = n_; L_.kind = (next); } while (0)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FCU_LV_LONG(L_, cand) do { if (!SER && __builtin_amdgcn_ballot_w64(cand)) L_.kind = 2; } while (0)
+#else                                                         /* host pass over the device code: parsed, never run */
+#define FCU_LV_LONG(L_, cand) do { if (!SER && (cand)) L_.kind = 2; } while (0)
+#endif
+#define FCU_LV_OWN(L_) do { if (SER) break; L_.ts = clock64(); L_.n_own++; } while (0)
+#define FCU_LV_SEC(L_, acc) do { if (SER) break; const long long n_ = clock64(); L_.acc += (unsigned long long)(n_ - L_.ts); L_.ts = n_; } while (0)
+#define FCU_LV_END(P_, L_) do { if (!SER && threadIdx.x == 0) { unsigned long long *f_ = ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof; \
+    f_[0] += L_.grp + ((unsigned long long)L_.n_grp << 40); f_[11] += L_.sht + ((unsigned long long)L_.n_sht << 40); f_[12] += L_.lng + ((unsigned long long)L_.n_lng << 40); \
+    f_[13] += L_.s0 + ((unsigned long long)L_.n_own << 40); f_[14] += L_.s1; f_[15] += L_.s2; f_[1] += (unsigned long long)(clock64() - L_.t0) + (1ull << 40); } } while (0)
+#else
+#define FCU_LV_BEGIN(p) do { } while (0)
+#define FCU_LV_TOP(p, next) do { } while (0)
+#define FCU_LV_LONG(p, cand) do { } while (0)
+#define FCU_LV_OWN(p) do { } while (0)
+#define FCU_LV_SEC(p, acc) do { } while (0)
+#define FCU_LV_END(P_, p) do { } while (0)
 #endif
 namespace fcu {
 
@@ -873,6 +907,75 @@ FCU_DEV int rdoq_qbits(int log2, int qp) { return 14 + qp / 6 + (15 - 8 - log2);
 FCU_DEV int level_nonzero(int32_t ld, int qbits) { return iabs(ld) >= ((int32_t)1 << (qbits - 1)); }
 
 struct LevelBits { int g10, g11, g20, g21; };              /* greater1 / greater2 flag costs of the current contexts */
+/* The level choice of one coefficient with uiMaxAbsLevel > 0 and the rates its record needs, in one pass: xGetCodedLevel
+ * (TComTrQuant.cpp:2738-2794) and the xGetICRate calls of rateIncUp / rateIncDown (:2263-2270).  Under one (goRice, c1Idx,
+ * c2Idx) state xGetICRate (:2807-2881) of neighbouring levels shares everything but the level: the prefix / escape threshold
+ * baseLevel, the flag bits and the Rice threshold are formed once (LevelRate), and the bypass bins of coeff_abs_level_remaining
+ * come in closed form: below 3 << rice (symbol >> rice) + 1 + rice; from there on the reference's loop leaves `length` as the
+ * position of the top bit of symbol - (3 << rice) + (1 << rice), one clz, and the bins are 4 + 2 length - rice.  Three rates are
+ * formed, of uiMaxAbsLevel, uiMaxAbsLevel - 1 and the one outer neighbour of the chosen level; every expression that yields a
+ * double has the operands and the order of the reference.  -DFCU_RDOQ_LEVELS_REF builds rdoq() and rdoq_wave() on coded_level()
+ * and ic_rate() below instead, which follow the reference call by call and are the definition; -DFCU_EMU_CHECK_RDOQ_LEVELS
+ * (emulator only, tests/emu/rdoq_level_emu.cpp) runs them next to level_choice() on every such coefficient and aborts unless
+ * level, costs (bit patterns), rateIncUp / rateIncDown and deltaU agree. */
+struct LevelRate { uint32_t base, rice, thr; int esc, one, two; };
+FCU_DEV LevelRate level_rate_state(const LevelBits &b, uint32_t goRice, uint32_t c1Idx, uint32_t c2Idx)
+{
+  LevelRate s;
+  s.base = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1; s.rice = goRice; s.thr = 3u << goRice;
+  s.esc = 32768 + ((c1Idx < 8) ? b.g11 + ((c2Idx < 1) ? b.g21 : 0) : 0);   /* a level coded with a remainder: its flags are all 1 */
+  s.one = 32768 + b.g10; s.two = 32768 + b.g11 + b.g20;                   /* levels 1 and 2 below baseLevel */
+  return s;
+}
+FCU_DEV int level_rate(const LevelRate &s, uint32_t absLevel)
+{
+  if (absLevel >= s.base) {
+    const uint32_t symbol = absLevel - s.base; uint32_t bins;
+    if (symbol < s.thr) bins = (symbol >> s.rice) + 1 + s.rice;
+    else { const uint32_t length = 31u - (uint32_t)__builtin_clz(symbol - s.thr + (1u << s.rice)); bins = 4 + 2 * length - s.rice; }
+    return s.esc + (int)(bins << 15);
+  }
+  return absLevel == 0 ? 0 : (absLevel == 1 ? s.one : s.two);
+}
+struct LevelChoice { uint32_t level; int rup, rdn; };        /* the chosen level, rateIncUp, rateIncDown */
+/* maxAbsLevel > 0; sbit0 / sbit1: the bits of the significance flag in this coefficient's context; *codedCost, *codedCostSig
+ * as the caller initialised them (the reference leaves pdCostSig alone where no level beats MAX_DOUBLE) */
+FCU_DEV LevelChoice level_choice(double lambda, double *codedCost, const double *codedCost0, double *codedCostSig, int32_t levelDouble, uint32_t maxAbsLevel,
+                                 int sbit0, int sbit1, const LevelBits &lb, uint32_t goRice, uint32_t c1Idx, uint32_t c2Idx, int qbits, double errScale, int last)
+{
+  const LevelRate rs = level_rate_state(lb, goRice, c1Idx, c2Idx);
+  const int rateHi = level_rate(rs, maxAbsLevel), rateLo = level_rate(rs, maxAbsLevel - 1);
+  double currCostSig = 0; uint32_t bestAbs = 0;
+  if (!last && maxAbsLevel < 3) {
+    *codedCostSig = lambda * (double)sbit0;
+    *codedCost = *codedCost0 + *codedCostSig;
+  } else *codedCost = FCU_MAX_DOUBLE;
+  if (!last) currCostSig = lambda * (double)sbit1;
+  {
+    const double err = (double)(levelDouble - ((int32_t)maxAbsLevel << qbits));
+    double cost = err * err * errScale + lambda * (double)rateHi;
+    cost += currCostSig;
+    if (cost < *codedCost) { bestAbs = maxAbsLevel; *codedCost = cost; *codedCostSig = currCostSig; }
+  }
+  if (maxAbsLevel > 1) {
+    const double err = (double)(levelDouble - ((int32_t)(maxAbsLevel - 1) << qbits));
+    double cost = err * err * errScale + lambda * (double)rateLo;
+    cost += currCostSig;
+    if (cost < *codedCost) { bestAbs = maxAbsLevel - 1; *codedCost = cost; *codedCostSig = currCostSig; }
+  }
+  /* the chosen level is maxAbsLevel, maxAbsLevel - 1 or 0: two of the three rates of its record are rateHi and rateLo (the rate
+   * of level 0 is 0), the third is the rate of the neighbour on the far side.  It is formed at one place, from a selected level
+   * and ahead of the branches (unused where level 0 wins): lanes of a batch that chose differently then share one evaluation
+   * where a call in each branch would run one after the other */
+  LevelChoice o; o.level = bestAbs;
+  const int isHi = bestAbs == maxAbsLevel;
+  const int rateOut = level_rate(rs, isHi ? maxAbsLevel + 1 : (maxAbsLevel >= 2 ? maxAbsLevel - 2 : 0));
+  if (bestAbs == 0) { o.rup = lb.g10; o.rdn = 0; }
+  else if (isHi) { o.rup = rateOut - rateHi; o.rdn = rateLo - rateHi; }
+  else { o.rup = rateHi - rateLo; o.rdn = rateOut - rateLo; }
+  return o;
+}
+#if defined(FCU_RDOQ_LEVELS_REF) || defined(FCU_EMU_CHECK_RDOQ_LEVELS)
 FCU_DEV int ic_rate(const LevelBits &b, uint32_t absLevel, uint32_t goRice, uint32_t c1Idx, uint32_t c2Idx)
 {                                                          /* xGetICRate, TComTrQuant.cpp:2807-2881 */
   int rate = 32768;
@@ -917,6 +1020,64 @@ FCU_DEV uint32_t coded_level(CB cb, double lambda, double *codedCost, double *co
   }
   return bestAbs;
 }
+/* The record of one coefficient as rdoq() formed it before level_choice(): the level choice, then the rates of the chosen level's
+ * neighbours (two of them are among those of the level choice). */
+template <class CB>
+FCU_DEV LevelChoice level_choice_ref(CB cb, double lambda, double *codedCost, double *codedCost0, double *codedCostSig, int32_t levelDouble, uint32_t maxAbsLevel,
+                                     int ctxSig, const LevelBits &lb, uint32_t goRice, uint32_t c1Idx, uint32_t c2Idx, int qbits, double errScale, int last)
+{
+  int rateHi = 0, rateLo = 0;                                  /* xGetICRate(maxAbsLevel), (maxAbsLevel - 1) from the level choice */
+  LevelChoice o; o.rdn = 0;
+  o.level = coded_level(cb, lambda, codedCost, codedCost0, codedCostSig, levelDouble, maxAbsLevel, ctxSig, lb, goRice, c1Idx, c2Idx, qbits, errScale, last, &rateHi, &rateLo);
+  if (o.level > 0) {                                           /* the chosen level is maxAbsLevel or maxAbsLevel - 1: one new rate, not three */
+    if (o.level == maxAbsLevel) {
+      o.rup = ic_rate(lb, o.level + 1, goRice, c1Idx, c2Idx) - rateHi;
+      o.rdn = (maxAbsLevel > 1 ? rateLo : ic_rate(lb, 0, goRice, c1Idx, c2Idx)) - rateHi;
+    } else {
+      o.rup = rateHi - rateLo;
+      o.rdn = ic_rate(lb, o.level - 1, goRice, c1Idx, c2Idx) - rateLo;
+    }
+  } else o.rup = lb.g10;
+  return o;
+}
+#endif
+#ifdef FCU_EMU_CHECK_RDOQ_LEVELS
+/* test bookkeeping (tests/test_rdoq_level_emu.py, tests/emu/rdoq_level_asan_driver.cpp): the cases the level choices of a run met.
+ * uiMaxAbsLevel 1 / 2 / 3 and more; the level below uiMaxAbsLevel chosen (not 0); level 0 chosen; the last position; c1Idx >= 8
+ * (baseLevel 1); c2Idx >= 1; Rice parameter 0 / 4; a rate of a symbol equal to / above 3 << rice (the escape branch); a symbol
+ * of 32768 or more, which the clipped levels cannot form (must stay 0) */
+enum { LEVEL_MAX1, LEVEL_MAX2, LEVEL_MAX3UP, LEVEL_CHOSE_LOWER, LEVEL_CHOSE_ZERO, LEVEL_LAST, LEVEL_C1IDX_8UP, LEVEL_C2IDX_1UP, LEVEL_RICE0, LEVEL_RICE4,
+       LEVEL_ESCAPE_AT, LEVEL_ESCAPE_ABOVE, LEVEL_SYMBOL_32768UP, LEVEL_N };
+extern "C" { __attribute__((weak)) unsigned long long fcu_emu_level_cnt[LEVEL_N]; }
+/* got / cc / cs: what level_choice() returned and left in the caller's costs (both 0 before the call, as in every caller) */
+template <class CB>
+static void level_choice_check(CB cb, int ctxSig, const LevelChoice &got, double cc, double c0, double cs, double lambda, int32_t levelDouble, uint32_t maxAbsLevel,
+                               const LevelBits &lb, uint32_t goRice, uint32_t c1Idx, uint32_t c2Idx, int qbits, double errScale, int last)
+{
+  double rcc = 0, rc0 = c0, rcs = 0;
+  const LevelChoice ref = level_choice_ref(cb, lambda, &rcc, &rc0, &rcs, levelDouble, maxAbsLevel, ctxSig, lb, goRice, c1Idx, c2Idx, qbits, errScale, last);
+  const int32_t du = (int32_t)((levelDouble - ((int32_t)got.level << qbits)) >> (qbits - 8)), rdu = (int32_t)((levelDouble - ((int32_t)ref.level << qbits)) >> (qbits - 8));
+  if (got.level != ref.level || memcmp(&cc, &rcc, 8) || memcmp(&c0, &rc0, 8) || memcmp(&cs, &rcs, 8) || got.rup != ref.rup || got.rdn != ref.rdn || du != rdu) {
+    fprintf(stderr, "FCU_EMU_CHECK_RDOQ_LEVELS: level_choice differs from coded_level + ic_rate (levelDouble %d max %u rice %u c1Idx %u c2Idx %u last %d: level %u / %u, "
+            "cc %a / %a, c0 %a / %a, cs %a / %a, up %d / %d, dn %d / %d, du %d / %d)\n", levelDouble, maxAbsLevel, goRice, c1Idx, c2Idx, last, got.level, ref.level,
+            cc, rcc, c0, rc0, cs, rcs, got.rup, ref.rup, got.rdn, ref.rdn, du, rdu);
+    abort();
+  }
+  unsigned long long *n = fcu_emu_level_cnt;
+  n[maxAbsLevel == 1 ? LEVEL_MAX1 : (maxAbsLevel == 2 ? LEVEL_MAX2 : LEVEL_MAX3UP)]++;
+  n[LEVEL_CHOSE_LOWER] += got.level > 0 && got.level == maxAbsLevel - 1; n[LEVEL_CHOSE_ZERO] += got.level == 0; n[LEVEL_LAST] += last != 0;
+  n[LEVEL_C1IDX_8UP] += c1Idx >= 8; n[LEVEL_C2IDX_1UP] += c2Idx >= 1; n[LEVEL_RICE0] += goRice == 0; n[LEVEL_RICE4] += goRice == 4;
+  const uint32_t base = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
+  const uint32_t lv[3] = { maxAbsLevel, maxAbsLevel - 1, got.level == maxAbsLevel ? maxAbsLevel + 1 : (maxAbsLevel >= 2 ? maxAbsLevel - 2 : 0) };   /* the rates level_choice() formed */
+  for (int k = 0; k < 3; k++) if (lv[k] >= base) {
+    const uint32_t symbol = lv[k] - base;
+    n[LEVEL_ESCAPE_AT] += symbol == (3u << goRice); n[LEVEL_ESCAPE_ABOVE] += symbol > (3u << goRice); n[LEVEL_SYMBOL_32768UP] += symbol >= 32768u;
+  }
+}
+#define FCU_CHECK_LEVELS(...) level_choice_check(__VA_ARGS__)
+#else
+#define FCU_CHECK_LEVELS(...) do { } while (0)
+#endif
 /* `c` is the coder whose contexts estBit() would snapshot (TEncSbac.cpp:1722-1956); cbfCtx
  * is the QT-CBF context of this TU (getCtxQtCbf + getCBFContextOffset).
  * src[sp*st] = level_double() of the coefficient at scan position sp; dst[sp*st] receives its level.
@@ -1175,6 +1336,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
     for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[(cgTop * 16 + k) * st]); nxt[k] = srcg[(cgTop * 16 + k) * st]; }
     FCU_WALK_COUNT(WALK_RDOQ_CALLS, 1); FCU_WALK_COUNT(WALK_RDOQ_TOP_IS_GROUP0, cgTop == 0);
   } else ahead = srcg[(cgTop * 16 + 15) * st];
+  FCU_LV_BEGIN(lv_);
   for (int cgScanPos = cgTop; cgScanPos >= 0; cgScanPos--) {
     if (GRP) {
 #pragma unroll
@@ -1200,6 +1362,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
     const uint32_t cntBits = g_hot.cnt_bits[pattern];
     for (int posInCG = 15; posInCG >= 0; posInCG--) {
       const int scanPos = cgScanPos * 16 + posInCG;
+      FCU_LV_TOP(lv_, 1);
       int32_t levelDouble;
       if (GRP) levelDouble = iabs(g_S.rq_grp[posInCG][slot]);
       else {
@@ -1208,6 +1371,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
       }
       uint32_t maxAbsLevel = (uint32_t)((levelDouble + ((int32_t)1 << (qbits - 1))) >> qbits);
       if (maxAbsLevel > 32767u) maxAbsLevel = 32767u;
+      FCU_LV_LONG(lv_, maxAbsLevel > 0);
       const double err = (double)levelDouble;
       double c0 = err * err * errScale, cc = 0, cs = 0;
       blockUncodedCost += c0;
@@ -1241,24 +1405,30 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
         } else {
           const int absCtx = CTX_ABS + (int)ctxSet + c2;
           LevelBits lb; lb.g10 = g10; lb.g11 = cb(oneCtx, 1); lb.g20 = cb(absCtx, 0); lb.g21 = cb(absCtx, 1);
-          int rateHi = 0, rateLo = 0;                          /* xGetICRate(maxAbsLevel), (maxAbsLevel - 1) from the level choice */
-          if (scanPos == lastScanPos)
-            level = coded_level(cb, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel,
-                                sigOff, lb, goRice, c1Idx, c2Idx, qbits, errScale, 1, &rateHi, &rateLo);
-          else {
-            level = coded_level(cb, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel,
-                                ctxSig, lb, goRice, c1Idx, c2Idx, qbits, errScale, 0, &rateHi, &rateLo);
-            sdel = sbit1 - sbit0;
-          }
-          if (level > 0) {                                     /* the chosen level is maxAbsLevel or maxAbsLevel - 1: one new rate, not three */
-            if (level == maxAbsLevel) {
-              rup = ic_rate(lb, level + 1, goRice, c1Idx, c2Idx) - rateHi;
-              rdn = (maxAbsLevel > 1 ? rateLo : ic_rate(lb, 0, goRice, c1Idx, c2Idx)) - rateHi;
+          const int isLast = scanPos == lastScanPos;
+          FCU_LV_OWN(lv_);
+#ifdef FCU_RDOQ_LEVELS_REF                                      /* level_choice_ref(), written out for the timer between its two parts */
+          int rateHi = 0, rateLo = 0;
+          LevelChoice lc; lc.rdn = 0;
+          lc.level = coded_level(cb, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, isLast ? sigOff : ctxSig, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast, &rateHi, &rateLo);
+          FCU_LV_SEC(lv_, s0);
+          if (lc.level > 0) {
+            if (lc.level == maxAbsLevel) {
+              lc.rup = ic_rate(lb, lc.level + 1, goRice, c1Idx, c2Idx) - rateHi;
+              lc.rdn = (maxAbsLevel > 1 ? rateLo : ic_rate(lb, 0, goRice, c1Idx, c2Idx)) - rateHi;
             } else {
-              rup = rateHi - rateLo;
-              rdn = ic_rate(lb, level - 1, goRice, c1Idx, c2Idx) - rateLo;
+              lc.rup = rateHi - rateLo;
+              lc.rdn = ic_rate(lb, lc.level - 1, goRice, c1Idx, c2Idx) - rateLo;
             }
-          } else rup = lb.g10;
+          } else lc.rup = lb.g10;
+          FCU_LV_SEC(lv_, s1);
+#else
+          const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+          FCU_CHECK_LEVELS(cb, isLast ? sigOff : ctxSig, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+          FCU_LV_SEC(lv_, s0);
+#endif
+          level = lc.level; rup = lc.rup; rdn = lc.rdn;
+          if (!isLast) sdel = sbit1 - sbit0;
         }
         RdoqRec r; r.cc = cc; r.cs = cs; r.c0 = c0; r.up = rup; r.dn = rdn; r.sd = sdel;
         r.du = (int32_t)((levelDouble - ((int32_t)level << qbits)) >> (qbits - 8));
@@ -1269,6 +1439,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
         if (level >= 1) c1Idx++;
         if (level > 1) { c1 = 0; c2 += (c2 < 2); c2Idx++; }
         else if (c1 < 3 && c1 > 0 && level) c1++;
+        FCU_LV_SEC(lv_, s2);
       } else baseCost += c0;
       if (SER) g_S.rq_lv[posInCG] = (int16_t)level; else dstg[scanPos * st] = (int16_t)level;
       rdSigCost += cs;
@@ -1280,6 +1451,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
         if (posInCG != 0) nnzBeforePos0++;
       }
     }
+    FCU_LV_TOP(lv_, 0);
     if (lastScanPos >= 0 && cgScanPos > 0) {                 /* context set of the next group (:2306-2316), once the last position is known */
       ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (cgScanPos - 1) > 0) ? 2 : 0) + (c1 == 0));
       c1 = 1; c2 = 0; c1Idx = 0; c2Idx = 0; goRice = 0;
@@ -1316,6 +1488,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
     }
   }
   FCU_RTOC(P, rt_, 12);                                       /* main loop */
+  FCU_LV_TOP(lv_, 0); FCU_LV_END(P, lv_);
   if (lastScanPos < 0) { RdoqOut z = { 0, -1 }; return z; }
 #ifdef FCU_EMU
   FCU_WALK_COUNT(WALK_RDOQ_ONLY_GROUP0, GRP && lastScanPos < 16);
@@ -1525,24 +1698,15 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
         int sdel = 0, rup, rdn = 0;
         const int absCtx = CTX_ABS + (int)ctxSet + c2;
         LevelBits lb4; lb4.g10 = g10; lb4.g11 = cb(oneCtx, 1); lb4.g20 = cb(absCtx, 0); lb4.g21 = cb(absCtx, 1);
-        int rateHi = 0, rateLo = 0;                            /* xGetICRate(maxAbsLevel), (maxAbsLevel - 1) from the level choice */
-        if (scanPos == lastScanPos)
-          level = coded_level(cbs, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel,
-                              0, lb4, goRice, c1Idx, c2Idx, qbits, errScale, 1, &rateHi, &rateLo);
-        else {
-          level = coded_level(cbs, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel,
-                              0, lb4, goRice, c1Idx, c2Idx, qbits, errScale, 0, &rateHi, &rateLo);
-          sdel = sbit1 - sbit0;
-        }
-        if (level > 0) {                                       /* the chosen level is maxAbsLevel or maxAbsLevel - 1: one new rate, not three */
-          if (level == maxAbsLevel) {
-            rup = ic_rate(lb4, level + 1, goRice, c1Idx, c2Idx) - rateHi;
-            rdn = (maxAbsLevel > 1 ? rateLo : ic_rate(lb4, 0, goRice, c1Idx, c2Idx)) - rateHi;
-          } else {
-            rup = rateHi - rateLo;
-            rdn = ic_rate(lb4, level - 1, goRice, c1Idx, c2Idx) - rateLo;
-          }
-        } else rup = lb4.g10;
+        const int isLast = scanPos == lastScanPos;
+#ifdef FCU_RDOQ_LEVELS_REF
+        const LevelChoice lc = level_choice_ref(cbs, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, 0, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+#else
+        const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+        FCU_CHECK_LEVELS(cbs, 0, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+#endif
+        level = lc.level; rup = lc.rup; rdn = lc.rdn;
+        if (!isLast) sdel = sbit1 - sbit0;
         vCc.put(ln, cc); vCs.put(ln, cs); vC0.put(ln, c0); vUp.put(ln, rup); vDn.put(ln, rdn); vSd.put(ln, sdel);
         vDu.put(ln, (int32_t)((levelDouble - ((int32_t)level << qbits)) >> (qbits - 8)));
         baseCost += cc;
