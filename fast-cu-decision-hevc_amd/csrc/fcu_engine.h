@@ -151,6 +151,9 @@ template <class T> __device__ inline T fcu_uni(T v)
     else FCU_ATOMIC_ADD(&g_S.vc_dist[v], (uint32_t)((e) * (e))); } while (0)
 #define FCU_SERIAL FCU_FOR_LANES if (lane == 0)
 /* section timers (diagnostic build only: -DFCU_PROFILE; shader-clock ticks summed per chain by lane 0) */
+#if defined(FCU_PROFILE_RDOQ) && ((FCU_PROFILE_RDOQ + 0) < 2 || (FCU_PROFILE_RDOQ + 0) > 4)
+#error "-DFCU_PROFILE_RDOQ takes a value: 2 (rdoq() on lane 0), 3 (the passes of rdoq_wave) or 4 (the level choice of rdoq())"
+#endif
 #if defined(FCU_PROFILE) && !defined(FCU_EMU)
 #define FCU_TIC(v) const long long v = clock64()
 #ifdef FCU_PROFILE_RQT   /* inter residual quadtree variant: slots 0..8 belong to the stages of inter_tu_trials / est_inter_residual_qt (FCU_QTOC); 10 stays the CTU total */
@@ -165,10 +168,10 @@ template <class T> __device__ inline T fcu_uni(T v)
 #elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 3   /* rdoq_wave variant: every slot but 10 (the CTU total) belongs to the sub-timers of rdoq_wave (FCU_WTOC) */
 #define FCU_TOC(E_, v, idx) do { if ((idx) == 10 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
-#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 4   /* level-choice variant: slots 2, 8 and 10 keep their sections and 13 (chroma_rdoq) moves to 3; the others belong to the coefficient loop of rdoq<0> (FCU_LV_*) */
+#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 4   /* level-choice variant: slots 2, 8 and 10 keep their sections and 13 (chroma_rdoq) moves to 3; the others belong to the coefficient loop of rdoq() (FCU_LV_*) */
 #define FCU_TOC(E_, v, idx) do { if (((idx) == 2 || (idx) == 8 || (idx) == 10 || (idx) == 13) && threadIdx.x == 0) (E_).C->prof[(idx) == 13 ? 3 : (idx)] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
-#elif defined(FCU_PROFILE_RDOQ) || defined(FCU_PROFILE_DEPTH)   /* slots 11..15 belong to the sub-timers inside the serial RDOQ (FCU_PROFILE_DEPTH: 11..14 to the time spent at CU depth 0..3 without its sub-CUs) in these variants */
+#elif defined(FCU_PROFILE_RDOQ) || defined(FCU_PROFILE_DEPTH)   /* slots 11..15 belong to the sub-timers of rdoq() on lane 0, -DFCU_PROFILE_RDOQ=2 (FCU_PROFILE_DEPTH: 11..14 to the time spent at CU depth 0..3 without its sub-CUs) in these variants */
 #define FCU_TOC(E_, v, idx) do { if ((idx) < 11 && threadIdx.x == 0) (E_).C->prof[idx] += (unsigned long long)(clock64() - v); } while (0)
 #define FCU_COUNT(E_, idx, n) do { } while (0)
 #elif defined(FCU_PROFILE_RMD)   /* RMD variant: slots 11..14 belong to the sub-timers of rmd() and to the reference build of the first pass (FCU_MTOC) */
@@ -232,10 +235,10 @@ __shared__ HotTables g_hot;
 
 #if defined(FCU_PROFILE_RQT) && !defined(FCU_EMU)     /* lane 0 of the lane-private RDOQ (the luma variant of an inter TU): slots 11..15 */
 #define FCU_RTIC(v) long long v = clock64()
-#define FCU_RTOC(P_, v, idx) do { if (!SER && threadIdx.x == 0) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
-#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) != 3 && (FCU_PROFILE_RDOQ + 0) != 4 && !defined(FCU_EMU)      /* -DFCU_PROFILE_RDOQ: the serial form; -DFCU_PROFILE_RDOQ=2: lane 0 of the lane-private form (rdoq<0>) */
+#define FCU_RTOC(P_, v, idx) do { if (threadIdx.x == 0) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
+#elif defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 2 && !defined(FCU_EMU)      /* -DFCU_PROFILE_RDOQ=2: lane 0 of the lane-private RDOQ, rdoq() */
 #define FCU_RTIC(v) long long v = clock64()
-#define FCU_RTOC(P_, v, idx) do { if ((FCU_PROFILE_RDOQ + 0) == 2 ? (!SER && threadIdx.x == 0) : SER) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
+#define FCU_RTOC(P_, v, idx) do { if (threadIdx.x == 0) { ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof[idx] += (unsigned long long)(clock64() - v); v = clock64(); } } while (0)
 #else
 #define FCU_RTIC(v) do { } while (0)
 #define FCU_RTOC(P_, v, idx) do { } while (0)
@@ -251,27 +254,29 @@ __shared__ HotTables g_hot;
 #define FCU_WTIC(v) do { } while (0)
 #define FCU_WTOC(P_, v, t, log2) do { } while (0)
 #endif
-/* -DFCU_PROFILE -DFCU_PROFILE_RDOQ=4: the coefficient loop of rdoq<0> on lane 0, by kind of iteration.  The ticks between two
+/* -DFCU_PROFILE -DFCU_PROFILE_RDOQ=4: the coefficient loop of rdoq() on lane 0, by kind of iteration.  The ticks between two
  * iteration tops go to the kind of the iteration they follow: 1 = no lane of the batch has a candidate level (uiMaxAbsLevel 0
  * on every active lane), 2 = at least one lane takes the level choice; 0 = the head and tail of a coefficient group.  Inside the
  * level choice, when lane 0 itself takes it: the level choice (xGetCodedLevel), the rates of rateIncUp / rateIncDown, and the
  * record store with the c1 / c2 / Rice update.  Sums stay in registers and reach the chain once per call: slots 0, 11, 12 =
  * group / short / long iterations and 13 = level choice, each ticks + (count << 40); 14, 15 = rates, store + update; 1 = the
- * call up to the end of the walk + (calls << 40).  tests/prof_run_rdoq_level.py prints them. */
+ * call up to the end of the walk + (calls << 40).  tests/prof_run_rdoq_level.py prints them.  Slot 14 stays 0: level_choice() forms
+ * the rates in the pass of the level choice, and with -DFCU_RDOQ_LEVELS_REF rdoq() calls level_choice_ref() as rdoq_wave() does,
+ * so level choice and rates are one section (13) in that build too. */
 #if defined(FCU_PROFILE_RDOQ) && (FCU_PROFILE_RDOQ + 0) == 4 && !defined(FCU_EMU)
 struct LvProf { long long t0, t, ts; unsigned long long grp, sht, lng, s0, s1, s2; unsigned n_grp, n_sht, n_lng, n_own; int kind; };
 #define FCU_LV_BEGIN(L_) LvProf L_ = { }; L_.t0 = L_.t = clock64()
-#define FCU_LV_TOP(L_, next) do { if (SER) break; const long long n_ = clock64(); const unsigned long long d_ = (unsigned long long)(n_ - L_.t); \
+#define FCU_LV_TOP(L_, next) do { const long long n_ = clock64(); const unsigned long long d_ = (unsigned long long)(n_ - L_.t); \
     if (L_.kind == 0) { L_.grp += d_; L_.n_grp++; } else if (L_.kind == 1) { L_.sht += d_; L_.n_sht++; } else { L_.lng += d_; L_.n_lng++; } \
     L_.t = n_; L_.kind = (next); } while (0)
 #if defined(__HIP_DEVICE_COMPILE__)
-#define FCU_LV_LONG(L_, cand) do { if (!SER && __builtin_amdgcn_ballot_w64(cand)) L_.kind = 2; } while (0)
+#define FCU_LV_LONG(L_, cand) do { if (__builtin_amdgcn_ballot_w64(cand)) L_.kind = 2; } while (0)
 #else                                                         /* host pass over the device code: parsed, never run */
-#define FCU_LV_LONG(L_, cand) do { if (!SER && (cand)) L_.kind = 2; } while (0)
+#define FCU_LV_LONG(L_, cand) do { if (cand) L_.kind = 2; } while (0)
 #endif
-#define FCU_LV_OWN(L_) do { if (SER) break; L_.ts = clock64(); L_.n_own++; } while (0)
-#define FCU_LV_SEC(L_, acc) do { if (SER) break; const long long n_ = clock64(); L_.acc += (unsigned long long)(n_ - L_.ts); L_.ts = n_; } while (0)
-#define FCU_LV_END(P_, L_) do { if (!SER && threadIdx.x == 0) { unsigned long long *f_ = ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof; \
+#define FCU_LV_OWN(L_) do { L_.ts = clock64(); L_.n_own++; } while (0)
+#define FCU_LV_SEC(L_, acc) do { const long long n_ = clock64(); L_.acc += (unsigned long long)(n_ - L_.ts); L_.ts = n_; } while (0)
+#define FCU_LV_END(P_, L_) do { if (threadIdx.x == 0) { unsigned long long *f_ = ((Chain *)((char *)&(P_) - __builtin_offsetof(Chain, p)))->prof; \
     f_[0] += L_.grp + ((unsigned long long)L_.n_grp << 40); f_[11] += L_.sht + ((unsigned long long)L_.n_sht << 40); f_[12] += L_.lng + ((unsigned long long)L_.n_lng << 40); \
     f_[13] += L_.s0 + ((unsigned long long)L_.n_own << 40); f_[14] += L_.s1; f_[15] += L_.s2; f_[1] += (unsigned long long)(clock64() - L_.t0) + (1ull << 40); } } while (0)
 #else
@@ -458,16 +463,14 @@ struct Shared {
    * [CAB_LUMA] the coder after the walk of the luma encoding est_intra_pred_luma chose for a 2Nx2N CU */
   Cabac cab[1 + (MAXDEPTH + 1) + MAXLC + 1];
   uint8_t ref5[5][68]; int dc5[5]; uint32_t cm_dist[5];     /* chroma: per-mode reference samples (N <= 16) */
-  /* Four tenants that are never live together (the union is 1 280 B, the size of rq_grp; 1 040 B before that one came;
+  /* Three tenants that are never live together (the union is 1 280 B, the size of rq_grp;
    * 8 688 B of LDS per chain in all = 16 chains per CU, four waves per SIMD):
    *  - reference samples of the block being predicted (+ the availability flags that build them): dead once the
    *    predictions of the batch are in the candidate pools, i.e. before any quantisation;
-   *  - the records of the coefficient group in flight in the serial RDOQ;
    *  - per lane the level_double values of the coefficient group a lane-private RDOQ is walking;
    *  - the |level| lists of the lane-private bit counters. */
   union {
     int16_t lane_abs[MAXLC][32];                    /* per lane: |level| list of the coefficient group being coded [0..15], the group's levels [16..31] */
-    RdoqRec rq_rec[16];                             /* serial RDOQ: records of the coefficient group in flight */
     int32_t rq_grp[16][MAXVC];                      /* lane-private RDOQ: the group being walked, position-major (a read by all lanes is conflict-free) */
     struct {
       int32_t colsum[128];                          /* availability flags of build_ref / chroma_leaf_refs5 */
@@ -477,10 +480,7 @@ struct Shared {
       };
     };
   };
-  union {
-    int16_t rq_lv[16];                              /* serial RDOQ: levels of the coefficient group in flight */
-    uint32_t sad[36];                               /* RMD SATD per mode; [35] SSE accumulator of a TU trial */
-  };
+  uint32_t sad[36];                                 /* RMD SATD per mode; [35] SSE accumulator of a TU trial */
   int dc;
   /* hand-over of ref / reff / dc from rmd() to the first pass of the same PU: ref_key(x, y, log2) of the luma block whose
    * samples they hold, or -1.  Set by rmd() only; build_ref and chroma_leaf_refs5 (which overwrite the arrays) clear it, the
@@ -707,7 +707,7 @@ FCU_DEV int coef_remain_bins(uint32_t symbol, uint32_t rparam)             /* by
 #ifdef FCU_EMU
 /* test bookkeeping of the emulator (tests/test_walk_prefetch_emu.py, tests/emu/walk_asan_driver.cpp; SMALL_*:
  * tests/test_small_tu_emu.py, the edge cases of the 4x4 / 8x8 trials): how often the lane-private
- * walks met their edge cases, and the bounds of the pool rdoq<0> loads from (set by compress_ctu): every address its group loads
+ * walks met their edge cases, and the bounds of the pool rdoq() loads from (set by compress_ctu): every address its group loads
  * form is checked against them, because the pools are members of one Scratch block and no sanitizer sees one run into the next */
 enum { WALK_RDOQ_CALLS, WALK_RDOQ_TOP_IS_GROUP0, WALK_RDOQ_AHEAD_GROUPS, WALK_RDOQ_ONLY_GROUP0, WALK_RDOQ_ONLY_LAST_GROUP, WALK_RDOQ_ALL_ZERO,
        WALK_BITS_CALLS, WALK_BITS_ONE_EMPTY_RUN_BETWEEN, WALK_BITS_SECOND_ROUND, WALK_N };
@@ -737,11 +737,11 @@ static const int32_t *g_emu_lscan_lo = nullptr, *g_emu_lscan_hi = nullptr;
  * linearly.  `last` = scan position of the last non-zero level, or -1: find it here (returns at once on an
  * all-zero TU).  The significant-group flags the reference gathers in its first loop (:1255-1275) are
  * derived group by group on the way down (a group's right/below neighbours come earlier in reverse scan). */
-/* SER = 1: called by one lane (serial sections): every argument is wave-uniform */
-template <int SER>
+/* ONE_LANE = 1: called by one lane (serial sections): every argument is wave-uniform */
+template <int ONE_LANE>
 FCU_DEV FCU_INLINE void code_coeff_body(int c, const int16_t *coef, int st, int last, int log2, int comp, int scanType, int tsFlag, const Params &P_, int16_t *absCoeff)
 {
-  if (SER) { c = FCU_UNI(c); coef = FCU_UNI(coef); last = FCU_UNI(last); scanType = FCU_UNI(scanType); tsFlag = FCU_UNI(tsFlag); absCoeff = FCU_UNI(absCoeff); }
+  if (ONE_LANE) { c = FCU_UNI(c); coef = FCU_UNI(coef); last = FCU_UNI(last); scanType = FCU_UNI(scanType); tsFlag = FCU_UNI(tsFlag); absCoeff = FCU_UNI(absCoeff); }
   const Params &P = *FCU_UNI(&P_);
   st = FCU_UNI(st); log2 = FCU_UNI(log2); comp = FCU_UNI(comp);
   FCU_IN_LDS(absCoeff);
@@ -882,9 +882,9 @@ FCU_DEV FCU_INLINE void code_coeff_body(int c, const int16_t *coef, int st, int 
 #undef FCU_EP
 }
 
-template <int SER>
+template <int ONE_LANE>
 FCU_DEV FCU_NOINLINE void code_coeff_nxn(int c, const int16_t *coef, int st, int last, int log2, int comp, int scanType, int tsFlag, const Params &P, int16_t *absCoeff)
-{ code_coeff_body<SER>(c, coef, st, last, log2, comp, scanType, tsFlag, P, absCoeff); }
+{ code_coeff_body<ONE_LANE>(c, coef, st, last, log2, comp, scanType, tsFlag, P, absCoeff); }
 
 /* ======================================================================================== */
 /* RDOQ -- per-lane callable (TComTrQuant::xRateDistOptQuant, TComTrQuant.cpp:2033-2573)     */
@@ -1078,6 +1078,143 @@ static void level_choice_check(CB cb, int ctxSig, const LevelChoice &got, double
 #else
 #define FCU_CHECK_LEVELS(...) do { } while (0)
 #endif
+/* The rules of xRateDistOptQuant that both walks apply, rdoq() inside a lane loop and rdoq_wave() from wave-uniform code or a
+ * lane loop: each is defined here once.  They take and return values and touch neither the pools nor the lanes; what differs
+ * between the walks (where a group is staged, where records go, the order of the running sums) stays in the walks. */
+/* the loop-invariant numbers and tables of one call (:2033-2110) */
+struct RdoqSetup {
+  int ch, N, n2, qbits; double lambda, errScale;
+  const uint16_t *scan; const uint8_t *scanCG;                 /* scan position -> block position, of coefficients / of coefficient groups */
+  int wg, firstSig, sigOff, cgBase;                            /* groups per row; first significance context of the size, contexts of sig_coeff / coded_sub_block */
+  uint64_t scan4, map4;                                        /* the 4x4 scan and the 4x4 significance-context map as nibbles */
+};
+FCU_DEV FCU_INLINE RdoqSetup rdoq_setup(const Params &P, int log2, int comp, int scanType)
+{
+  RdoqSetup S;
+  S.ch = comp ? 1 : 0; S.N = 1 << log2; S.n2 = S.N * S.N;
+  S.qbits = rdoq_qbits(log2, comp ? P.qp_c : P.qp);
+  S.lambda = P.rdoq_lambda[comp];
+  S.errScale = P.err_scale[S.ch][log2 - 2];
+  S.scan = log2 == 2 ? &g_hot.scan[scanType][0] : k_scan + k_scan_off[scanType * 4 + log2 - 2];
+  S.scanCG = log2 <= 3 ? g_hot.scan_cg8[log2 == 2 ? 0 : scanType] : k_scan_cg + k_scan_cg_off[scanType * 4 + log2 - 2];
+  S.wg = S.N >> 2; S.firstSig = first_sig_ctx(log2, scanType, S.ch);
+  S.sigOff = CTX_SIG + (S.ch ? 28 : 0); S.cgBase = CTX_SIGCG + (S.ch ? 2 : 0);
+  S.scan4 = g_hot.scan4_nib[scanType]; S.map4 = g_hot.map4_nib;
+  return S;
+}
+/* The significance context of the coefficient at posInCG of a group (getSigCtxInc, TComTrQuant.cpp:2619-2718).  In a TU above
+ * 4x4 only DC and the three contexts sigBase + 0..2 occur: sigBase = sig_base_of() of the group, cntBits = g_hot.cnt_bits[] of
+ * its neighbour pattern. */
+FCU_DEV FCU_INLINE int sig_base_of(const RdoqSetup &S, int cgx, int cgy) { return S.sigOff + S.firstSig + ((!S.ch && (cgx + cgy) > 0) ? 3 : 0); }
+FCU_DEV FCU_INLINE int sig_ctx_of(const RdoqSetup &S, int log2, int scanPos, int posInCG, int sigBase, uint32_t cntBits)
+{
+  const int p4 = (int)((S.scan4 >> (4 * posInCG)) & 15);       /* position inside the 4x4 group (raster) from the packed 4x4 scan */
+  if (log2 == 2) return S.sigOff + (p4 ? (int)((S.map4 >> (4 * p4)) & 15) : 0);
+  if (scanPos == 0) return S.sigOff;
+  return sigBase + (int)((cntBits >> (2 * p4)) & 3);
+}
+/* the greater1 / greater2 / Rice state of the walk (:2190-2316): which contexts and which Rice parameter price the next level */
+struct LevelState { uint32_t ctxSet = 0, c1Idx = 0, c2Idx = 0, goRice = 0; int c1 = 1, c2 = 0; };
+/* the context set at the first candidate level, the block's last significant position (:2190-2196) */
+FCU_DEV FCU_INLINE void level_state_first(LevelState &s, int ch, int scanPos) { s.ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (scanPos >> 4) > 0) ? 2 : 0)); }
+/* after a coefficient whose level was chosen (:2272-2294) */
+FCU_DEV FCU_INLINE void level_state_advance(LevelState &s, uint32_t level)
+{
+  const uint32_t baseLevel = (s.c1Idx < 8) ? (2 + (s.c2Idx < 1)) : 1;
+  if (level >= baseLevel) { if (level > 3u * (1u << s.goRice)) s.goRice = s.goRice + 1 < 4 ? s.goRice + 1 : 4; }
+  if (level >= 1) s.c1Idx++;
+  if (level > 1) { s.c1 = 0; s.c2 += (s.c2 < 2); s.c2Idx++; }
+  else if (s.c1 < 3 && s.c1 > 0 && level) s.c1++;
+}
+/* at the end of group cgScanPos > 0, once the last position is known: the context set of the next group (:2306-2316) */
+FCU_DEV FCU_INLINE void level_state_next_group(LevelState &s, int ch, int cgScanPos)
+{
+  s.ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (cgScanPos - 1) > 0) ? 2 : 0) + (s.c1 == 0));
+  s.c1 = 1; s.c2 = 0; s.c1Idx = 0; s.c2Idx = 0; s.goRice = 0;
+}
+/* The decision of a coefficient group at the end of its walk (:2318-2358): the cost of its coded_sub_block_flag goes into
+ * baseCost, and a group whose levels cost more than leaving it empty is zeroed.  rdSigCost, rdSigCost0, rdCodedLevelandDist,
+ * rdUncodedDist, nnzBeforePos0: the group's sums as the walk left them.  Returns costCGSig of the group and whether it was
+ * zeroed; the caller then clears the group's levels and sets cc = c0, cs = 0 in the records of those that were not 0. */
+struct CgDecision { double cgSig; int zeroed; };
+template <class CB>
+FCU_DEV FCU_INLINE CgDecision cg_decide(CB cb, const RdoqSetup &S, int cgScanPos, int cgLastScanPos, int cgBlk, int cgx, int cgy, uint64_t &cgflag, double &baseCost,
+                                        double rdSigCost, double rdSigCost0, double rdCodedLevelandDist, double rdUncodedDist, int nnzBeforePos0)
+{
+  CgDecision d = { 0, 0 };
+  if (cgLastScanPos >= 0) {
+    if (cgScanPos) {
+      if (((cgflag >> cgBlk) & 1) == 0) {
+        const int ctxSig = S.cgBase + sig_cg_ctx(cgflag, cgx, cgy, S.wg);
+        baseCost += S.lambda * (double)cb(ctxSig, 0) - rdSigCost;
+        d.cgSig = S.lambda * (double)cb(ctxSig, 0);
+      } else if (cgScanPos < cgLastScanPos) {
+        if (nnzBeforePos0 == 0) { baseCost -= rdSigCost0; rdSigCost -= rdSigCost0; }
+        double costZeroCG = baseCost;
+        const int ctxSig = S.cgBase + sig_cg_ctx(cgflag, cgx, cgy, S.wg);
+        baseCost += S.lambda * (double)cb(ctxSig, 1);
+        costZeroCG += S.lambda * (double)cb(ctxSig, 0);
+        d.cgSig = S.lambda * (double)cb(ctxSig, 1);
+        costZeroCG += rdUncodedDist; costZeroCG -= rdCodedLevelandDist; costZeroCG -= rdSigCost;
+        if (costZeroCG < baseCost) {
+          cgflag &= ~(1ull << cgBlk); baseCost = costZeroCG;
+          d.cgSig = S.lambda * (double)cb(ctxSig, 0);
+          d.zeroed = 1;
+        }
+      }
+    } else cgflag |= 1ull << cgBlk;
+  }
+  return d;
+}
+/* lambda * xGetRateLast (TComTrQuant.cpp:2898-2916) of scan position scanPos, with estLastSignificantPositionBit
+ * (TEncSbac.cpp:1863-1923) evaluated on demand; LastCtx: what that estimate needs of the block, formed once per call */
+struct LastCtx { int lsh, lbx, lby, lgmax; };
+FCU_DEV FCU_INLINE LastCtx last_ctx_of(const RdoqSetup &S, int log2)
+{
+  const int lcc = log2 - 2, loff = S.ch ? 0 : (lcc * 3 + ((lcc + 1) >> 2));
+  LastCtx L; L.lsh = S.ch ? lcc : ((lcc + 3) >> 2);
+  L.lbx = CTX_LASTX + (S.ch ? 15 : 0) + loff; L.lby = CTX_LASTY + (S.ch ? 15 : 0) + loff; L.lgmax = g_hot.group_idx[S.N - 1];
+  return L;
+}
+template <class CB>
+FCU_DEV FCU_INLINE double rate_last(CB cb, const RdoqSetup &S, const LastCtx &L, int log2, int scanType, int scanPos)
+{
+  const int blk = S.scan[scanPos];
+  const int py = blk >> log2, px = blk - (py << log2);
+  const int ax = scanType == 2 ? py : px, ay = scanType == 2 ? px : py;
+  const int gx = g_hot.group_idx[ax], gy = g_hot.group_idx[ay];
+  int bxs = 0, bys = 0;
+  for (int k = 0; k < gx; k++) bxs += cb(L.lbx + (k >> L.lsh), 1);
+  if (gx < L.lgmax) bxs += cb(L.lbx + (gx >> L.lsh), 0);
+  for (int k = 0; k < gy; k++) bys += cb(L.lby + (k >> L.lsh), 1);
+  if (gy < L.lgmax) bys += cb(L.lby + (gy >> L.lsh), 0);
+  double r = (double)(bxs + bys);
+  if (gx > 3) r += 32768.0 * (double)((gx - 2) >> 1);
+  if (gy > 3) r += 32768.0 * (double)((gy - 2) >> 1);
+  return S.lambda * r;
+}
+/* Sign bit hiding (TComTrQuant.cpp:2478-2544): the price of changing the level at position n of a group by one, and in *change
+ * the direction that price is for.  lv and du, up, dn, sd: the level and its record; srcNeg: the source value is negative
+ * (looked at only where lv is 0 and n < firstNZ); firstNZ, lastNZ: the group's first and last non-zero positions, signbit: the
+ * sign of the level at firstNZ; lastCG == 1: the group holds the block's last level. */
+FCU_DEV FCU_INLINE long long sh_cost(int lv, int32_t du, int32_t up, int32_t dn, int32_t sd, int srcNeg, int n, int firstNZ, int lastNZ, int lastCG, uint32_t signbit,
+                                     long long rdFactor, int *change)
+{
+  const long long kInf = 0x7fffffffffffffffLL;
+  long long curCost;
+  if (lv != 0) {
+    const long long costUp = rdFactor * (-du) + up;
+    long long costDown = rdFactor * (du) + dn - ((iabs(lv) == 1) ? sd : 0);
+    if (lastCG == 1 && lastNZ == n && iabs(lv) == 1) costDown -= (4 << 15);
+    if (costUp < costDown) { curCost = costUp; *change = 1; }
+    else { *change = -1; if (n == firstNZ && iabs(lv) == 1) curCost = kInf; else curCost = costDown; }
+  } else {
+    curCost = rdFactor * (-(long long)(iabs(du))) + (1 << 15) + up + sd;
+    *change = 1;
+    if (n < firstNZ) { const uint32_t thissign = srcNeg ? 1 : 0; if (thissign != signbit) curCost = kInf; }
+  }
+  return curCost;
+}
 /* `c` is the coder whose contexts estBit() would snapshot (TEncSbac.cpp:1722-1956); cbfCtx
  * is the QT-CBF context of this TU (getCtxQtCbf + getCBFContextOffset).
  * src[sp*st] = level_double() of the coefficient at scan position sp; dst[sp*st] receives its level.
@@ -1150,20 +1287,18 @@ FCU_DEV FCU_NOINLINE RdoqOut quant_plain(const int32_t *src, int16_t *dst, int s
 /* The passes of xRateDistOptQuant after its first loop, shared by rdoq() and rdoq_wave(): the last significant position
  * (:2360-2436), the signs, sign bit hiding (:2442-2572). */
 template <class CB>
-FCU_DEV FCU_INLINE int rdoq_last_pos(CB cb, const FCU_HBM int16_t *dstg, const FCU_HBM RdoqRec *recg, const FCU_HBM double *cgg,
-                                     int st, int log2, int ch, int scanType, int cbfCtx, const uint16_t *scan, const uint8_t *scanCG,
-                                     uint64_t cgflag, int cgLastScanPos, int lastScanPos, double baseCost, double blockUncodedCost, double lambda)
+FCU_DEV FCU_INLINE int rdoq_last_pos(CB cb, const RdoqSetup &S, const FCU_HBM int16_t *dstg, const FCU_HBM RdoqRec *recg, const FCU_HBM double *cgg,
+                                     int st, int log2, int scanType, int cbfCtx,
+                                     uint64_t cgflag, int cgLastScanPos, int lastScanPos, double baseCost, double blockUncodedCost)
 {
-  const int N = 1 << log2;
+  const double lambda = S.lambda;
   double bestCost; int bestLastIdxP1 = 0;
   bestCost = blockUncodedCost + lambda * (double)cb(cbfCtx, 0);
   baseCost += lambda * (double)cb(cbfCtx, 1);
-  /* estLastSignificantPositionBit (TEncSbac.cpp:1863-1923) evaluated on demand */
-  const int lcc = log2 - 2, loff = ch ? 0 : (lcc * 3 + ((lcc + 1) >> 2)), lsh = ch ? lcc : ((lcc + 3) >> 2);
-  const int lbx = CTX_LASTX + (ch ? 15 : 0) + loff, lby = CTX_LASTY + (ch ? 15 : 0) + loff, lgmax = g_hot.group_idx[N - 1];
+  const LastCtx L = last_ctx_of(S, log2);
   int foundLast = 0;
   for (int cgScanPos = cgLastScanPos; cgScanPos >= 0; cgScanPos--) {
-    const int cgBlk = scanCG[cgScanPos];
+    const int cgBlk = S.scanCG[cgScanPos];
     baseCost -= cgg[cgScanPos * st];
     if ((cgflag >> cgBlk) & 1) {
       const int top = (cgScanPos * 16 + 15 > lastScanPos) ? lastScanPos - cgScanPos * 16 : 15;   /* positions above the last one are skipped */
@@ -1173,19 +1308,7 @@ FCU_DEV FCU_INLINE int rdoq_last_pos(CB cb, const FCU_HBM int16_t *dstg, const F
         const int lv = aLv; const double curCs = aCs;
         if (posInCG > 0) { aLv = dstg[(scanPos - 1) * st]; aCs = recg[(scanPos - 1) * st].cs; }
         if (lv) {
-          const int blk = scan[scanPos];
-          const int py = blk >> log2, px = blk - (py << log2);
-          const int ax = scanType == 2 ? py : px, ay = scanType == 2 ? px : py;
-          const int gx = g_hot.group_idx[ax], gy = g_hot.group_idx[ay];
-          int bxs = 0, bys = 0;
-          for (int k = 0; k < gx; k++) bxs += cb(lbx + (k >> lsh), 1);
-          if (gx < lgmax) bxs += cb(lbx + (gx >> lsh), 0);
-          for (int k = 0; k < gy; k++) bys += cb(lby + (k >> lsh), 1);
-          if (gy < lgmax) bys += cb(lby + (gy >> lsh), 0);
-          double r = (double)(bxs + bys);                                  /* xGetRateLast, TComTrQuant.cpp:2898-2916 */
-          if (gx > 3) r += 32768.0 * (double)((gx - 2) >> 1);
-          if (gy > 3) r += 32768.0 * (double)((gy - 2) >> 1);
-          const double costLast = lambda * r;
+          const double costLast = rate_last(cb, S, L, log2, scanType, scanPos);
           const double totalCost = baseCost + costLast - curCs;
           if (totalCost < bestCost) { bestLastIdxP1 = scanPos + 1; bestCost = totalCost; }
           if (lv > 1) { foundLast = 1; break; }
@@ -1232,21 +1355,12 @@ FCU_DEV FCU_INLINE void rdoq_sign_hiding(const Params &P, const FCU_HBM int32_t 
       if (lastNZ - firstNZ >= 4) {
         const uint32_t signbit = (negMask >> firstNZ) & 1;
         if (signbit != (uint32_t)(sum & 1)) {
-          long long minCostInc = 0x7fffffffffffffffLL, curCost = 0x7fffffffffffffffLL;
+          long long minCostInc = 0x7fffffffffffffffLL;
           int minPos = -1, finalChange = 0, curChange = 0;
           for (n = (lastCG == 1 ? lastNZ : 15); n >= 0; --n) {
             const int sp = n + subPos; const int lv = dstg[sp * st]; const RdoqRec q = recg[sp * st];
-            if (lv != 0) {
-              const long long costUp = rdFactor * (-q.du) + q.up;
-              long long costDown = rdFactor * (q.du) + q.dn - ((iabs(lv) == 1) ? q.sd : 0);
-              if (lastCG == 1 && lastNZ == n && iabs(lv) == 1) costDown -= (4 << 15);
-              if (costUp < costDown) { curCost = costUp; curChange = 1; }
-              else { curChange = -1; if (n == firstNZ && iabs(lv) == 1) curCost = 0x7fffffffffffffffLL; else curCost = costDown; }
-            } else {
-              curCost = rdFactor * (-(long long)(iabs(q.du))) + (1 << 15) + q.up + q.sd;
-              curChange = 1;
-              if (n < firstNZ) { const uint32_t thissign = srcg[sp * st] >= 0 ? 0 : 1; if (thissign != signbit) curCost = 0x7fffffffffffffffLL; }
-            }
+            const int srcNeg = (lv == 0 && n < firstNZ) ? srcg[sp * st] < 0 : 0;   /* loaded only where sh_cost() looks at it */
+            const long long curCost = sh_cost(lv, q.du, q.up, q.dn, q.sd, srcNeg, n, firstNZ, lastNZ, lastCG, signbit, rdFactor, &curChange);
             if (curCost < minCostInc) { minCostInc = curCost; finalChange = curChange; minPos = sp; }
           }
           const int old = dstg[minPos * st];
@@ -1259,17 +1373,18 @@ FCU_DEV FCU_INLINE void rdoq_sign_hiding(const Params &P, const FCU_HBM int32_t 
     }
   }
 }
-template <int SER, class CB>
-FCU_DEV FCU_INLINE RdoqOut rdoq_finish(CB cb, const Params &P, const FCU_HBM int32_t *srcg, FCU_HBM int16_t *dstg, FCU_HBM RdoqRec *recg, FCU_HBM double *cgg,
-                                       int st, int log2, int ch, int scanType, int cbfCtx, const uint16_t *scan, const uint8_t *scanCG,
-                                       uint64_t cgflag, int cgLastScanPos, int lastScanPos, double baseCost, double blockUncodedCost, double lambda)
+/* the tail of rdoq(), and the reference -DFCU_EMU_CHECK_RDOQ_TAIL runs next to the passes of rdoq_wave() */
+template <class CB>
+FCU_DEV FCU_INLINE RdoqOut rdoq_finish(CB cb, const Params &P, const RdoqSetup &S, const FCU_HBM int32_t *srcg, FCU_HBM int16_t *dstg, FCU_HBM RdoqRec *recg, FCU_HBM double *cgg,
+                                       int st, int log2, int scanType, int cbfCtx,
+                                       uint64_t cgflag, int cgLastScanPos, int lastScanPos, double baseCost, double blockUncodedCost)
 {
   FCU_RTIC(rt_);
-  const int bestLastIdxP1 = rdoq_last_pos(cb, dstg, recg, cgg, st, log2, ch, scanType, cbfCtx, scan, scanCG, cgflag, cgLastScanPos, lastScanPos, baseCost, blockUncodedCost, lambda);
+  const int bestLastIdxP1 = rdoq_last_pos(cb, S, dstg, recg, cgg, st, log2, scanType, cbfCtx, cgflag, cgLastScanPos, lastScanPos, baseCost, blockUncodedCost);
   FCU_RTOC(P, rt_, 13);                                       /* last-position search */
   const int absSum = rdoq_signs(srcg, dstg, st, bestLastIdxP1, lastScanPos);
   FCU_RTOC(P, rt_, 14);                                       /* signs */
-  rdoq_sign_hiding(P, srcg, dstg, recg, st, ch, bestLastIdxP1, absSum);
+  rdoq_sign_hiding(P, srcg, dstg, recg, st, S.ch, bestLastIdxP1, absSum);
   FCU_RTOC(P, rt_, 15);                                       /* sign hiding */
   int last = bestLastIdxP1 - 1;                              /* sign hiding may have cleared the last level */
   while (last >= 0 && dstg[last * st] == 0) last--;
@@ -1278,40 +1393,31 @@ FCU_DEV FCU_INLINE RdoqOut rdoq_finish(CB cb, const Params &P, const FCU_HBM int
 }
 
 
-template <int SER, int EST>
-/* slot (SER = 0): the caller's lane, < MAXVC: the column of g_S.rq_grp this walk stages its coefficient group in */
+template <int EST>
+/* called inside a lane loop, a candidate per lane.  slot: the caller's lane, < MAXVC: the column of g_S.rq_grp this walk stages
+ * its coefficient group in */
 FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int st, int topNZ, int log2, int comp, int scanType, int cbfCtx, const Params &P_, RdoqRec *rec, double *costCGSig, int slot = 0)
 {
   const Params &P = *FCU_UNI(&P_);
   st = FCU_UNI(st); log2 = FCU_UNI(log2); comp = FCU_UNI(comp); cbfCtx = FCU_UNI(cbfCtx);
-  if (SER) { c = FCU_UNI(c); src = FCU_UNI(src); dst = FCU_UNI(dst); topNZ = FCU_UNI(topNZ); scanType = FCU_UNI(scanType); rec = FCU_UNI(rec); costCGSig = FCU_UNI(costCGSig); }
   FCU_RTIC(rt_);
-  if (topNZ < 0) { FCU_WALK_COUNT(WALK_RDOQ_ALL_ZERO, !SER); RdoqOut z = { 0, -1 }; return z; }            /* every level is 0: the reference leaves with uiAbsSum 0 (:2330) */
+  if (topNZ < 0) { FCU_WALK_COUNT(WALK_RDOQ_ALL_ZERO, 1); RdoqOut z = { 0, -1 }; return z; }            /* every level is 0: the reference leaves with uiAbsSum 0 (:2330) */
   const FCU_HBM int32_t *srcg = (const FCU_HBM int32_t *)src; FCU_HBM int16_t *dstg = (FCU_HBM int16_t *)dst;
   FCU_HBM RdoqRec *recg = (FCU_HBM RdoqRec *)rec; FCU_HBM double *cgg = (FCU_HBM double *)costCGSig;
   auto cb = [&](int ctx, int bin) -> int { return EST ? (int)FCU_EST[ctx * 2 + bin] : ctx_bits(c, ctx, bin); };
-  const int ch = comp ? 1 : 0, N = 1 << log2, n2 = N * N;
-  const int qp = comp ? P.qp_c : P.qp;
-  const int qbits = rdoq_qbits(log2, qp);
-  const double lambda = P.rdoq_lambda[comp];
-  const double errScale = P.err_scale[ch][log2 - 2];
   /* the reference clears all seven arrays; only entries at scan positions <= the last significant one are
    * ever read back (last-position search, group zero-out, sign hiding), and each of those is written below */
-  const uint16_t *scan = log2 == 2 ? &g_hot.scan[scanType][0] : k_scan + k_scan_off[scanType * 4 + log2 - 2];
-  const uint8_t *scanCG = log2 <= 3 ? g_hot.scan_cg8[log2 == 2 ? 0 : scanType] : k_scan_cg + k_scan_cg_off[scanType * 4 + log2 - 2];
-  const int wg = N >> 2, firstSig = first_sig_ctx(log2, scanType, ch);
-  const int sigOff = CTX_SIG + (ch ? 28 : 0), cgBase = CTX_SIGCG + (ch ? 2 : 0);
+  const RdoqSetup S = rdoq_setup(P, log2, comp, scanType);
+  const int ch = S.ch, n2 = S.n2, qbits = S.qbits, wg = S.wg, sigOff = S.sigOff; const double lambda = S.lambda, errScale = S.errScale;
   uint64_t cgflag = 0;
-  int cgLastScanPos = -1; uint32_t ctxSet = 0; int c1 = 1, c2 = 0;
+  int cgLastScanPos = -1; LevelState ls;
   double baseCost = 0, blockUncodedCost = 0;
-  int lastScanPos = -1; uint32_t c1Idx = 0, c2Idx = 0, goRice = 0;
-  int absSum = 0;
+  int lastScanPos = -1;
 
-  const uint64_t scan4 = g_hot.scan4_nib[scanType], map4 = g_hot.map4_nib;
   int g10 = 0, g10Ctx = -1;
   /* coefficient groups above the last candidate level: only the uncoded cost accumulates (in scan order) */
   const int cgTop = topNZ >> 4;
-  for (int cg = (n2 >> 4) - 1; cg > cgTop; cg--) {              /* a group's sixteen loads first, then the adds in scan order */
+  for (int cg = (n2 >> 4) - 1; cg > cgTop; cg--) {            /* a group's sixteen loads first, then the adds in scan order */
     int32_t v[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = srcg[(cg * 16 + k) * st];
@@ -1320,40 +1426,33 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
   }
   baseCost = blockUncodedCost;
   FCU_RTOC(P, rt_, 11);                                       /* set-up + uncoded tail */
-  /* SER = 0: a group is fetched as a group: sixteen loads issued together, one round trip per group where the load one
-   * coefficient ahead paid a partly exposed round trip on every short iteration.  The loads of group cg - 1 are written at the
+  /* A group is fetched as a group: sixteen loads issued together, one round trip per group where a load one coefficient
+   * ahead pays a partly exposed round trip on every short iteration.  The loads of group cg - 1 are written at the
    * top of the walk of group cg, but that is NOT an overlap with the walk in the compiled kernel: the flat load of
    * scanCG[cgScanPos] follows them, loads retire in order, and its s_waitcnt vmcnt(0) waits for all sixteen.  (Reading scanCG
    * one group ahead through typed pointers does remove that wait, but a table read still stalls at the group top for TUs above
    * 8x8 and the private segment grows by 250 B: not shipped)  The values are parked in the lane's column of
-   * g_S.rq_grp, which the coefficient loop indexes (a register array indexed by the position would live in scratch memory).
-   * SER = 1 keeps the load one coefficient ahead. */
-  constexpr bool GRP = !SER;
-  int32_t ahead = 0, nxt[16];
-  if (GRP) {
-    FCU_CHECK(slot >= 0 && slot < MAXVC);
+   * g_S.rq_grp, which the coefficient loop indexes (a register array indexed by the position would live in scratch memory). */
+  int32_t nxt[16];
+  FCU_CHECK(slot >= 0 && slot < MAXVC);
 #pragma unroll
-    for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[(cgTop * 16 + k) * st]); nxt[k] = srcg[(cgTop * 16 + k) * st]; }
-    FCU_WALK_COUNT(WALK_RDOQ_CALLS, 1); FCU_WALK_COUNT(WALK_RDOQ_TOP_IS_GROUP0, cgTop == 0);
-  } else ahead = srcg[(cgTop * 16 + 15) * st];
+  for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[(cgTop * 16 + k) * st]); nxt[k] = srcg[(cgTop * 16 + k) * st]; }
+  FCU_WALK_COUNT(WALK_RDOQ_CALLS, 1); FCU_WALK_COUNT(WALK_RDOQ_TOP_IS_GROUP0, cgTop == 0);
   FCU_LV_BEGIN(lv_);
   for (int cgScanPos = cgTop; cgScanPos >= 0; cgScanPos--) {
-    if (GRP) {
 #pragma unroll
-      for (int k = 0; k < 16; k++) g_S.rq_grp[k][slot] = nxt[k];
-      if (cgScanPos > 0) {                                    /* group 0 has no successor: no address below scan position 0 is formed */
-        FCU_WALK_COUNT(WALK_RDOQ_AHEAD_GROUPS, 1);
+    for (int k = 0; k < 16; k++) g_S.rq_grp[k][slot] = nxt[k];
+    if (cgScanPos > 0) {                                      /* group 0 has no successor: no address below scan position 0 is formed */
+      FCU_WALK_COUNT(WALK_RDOQ_AHEAD_GROUPS, 1);
 #pragma unroll
-        for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[((cgScanPos - 1) * 16 + k) * st]); nxt[k] = srcg[((cgScanPos - 1) * 16 + k) * st]; }
-      }
+      for (int k = 0; k < 16; k++) { FCU_CHECK_LSCAN(&srcg[((cgScanPos - 1) * 16 + k) * st]); nxt[k] = srcg[((cgScanPos - 1) * 16 + k) * st]; }
     }
-    const int cgBlk = scanCG[cgScanPos], cgy = cgBlk / wg, cgx = cgBlk - cgy * wg;
+    const int cgBlk = S.scanCG[cgScanPos], cgy = cgBlk / wg, cgx = cgBlk - cgy * wg;
     double rdSigCost = 0, rdSigCost0 = 0, rdCodedLevelandDist = 0, rdUncodedDist = 0; int nnzBeforePos0 = 0;
     const int pattern = pattern_sig_ctx(cgflag, cgx, cgy, wg);
-    cgg[cgScanPos * st] = 0;
     /* The contexts are frozen during RDOQ (estBit snapshot, TEncSbac.cpp:1722-1956), so the significance costs of a
-     * group are loop invariants: in a TU > 4x4 only the three contexts sigBase + cnt occur besides DC (sig_ctx_inc). */
-    const int sigBase = sigOff + firstSig + ((!ch && (cgx + cgy) > 0) ? 3 : 0);
+     * group are loop invariants: in a TU > 4x4 only the three contexts sigBase + cnt occur besides DC (sig_ctx_of). */
+    const int sigBase = sig_base_of(S, cgx, cgy);
     int b00 = 0, b01 = 0, b02 = 0, b10 = 0, b11 = 0, b12 = 0;
     if (log2 > 2) {
       b00 = cb(sigBase, 0); b01 = cb(sigBase + 1, 0); b02 = cb(sigBase + 2, 0);
@@ -1363,12 +1462,7 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
     for (int posInCG = 15; posInCG >= 0; posInCG--) {
       const int scanPos = cgScanPos * 16 + posInCG;
       FCU_LV_TOP(lv_, 1);
-      int32_t levelDouble;
-      if (GRP) levelDouble = iabs(g_S.rq_grp[posInCG][slot]);
-      else {
-        levelDouble = iabs(ahead);
-        if (scanPos > 0) ahead = srcg[(scanPos - 1) * st];    /* one ahead: its latency overlaps this coefficient's work */
-      }
+      const int32_t levelDouble = iabs(g_S.rq_grp[posInCG][slot]);
       uint32_t maxAbsLevel = (uint32_t)((levelDouble + ((int32_t)1 << (qbits - 1))) >> qbits);
       if (maxAbsLevel > 32767u) maxAbsLevel = 32767u;
       FCU_LV_LONG(lv_, maxAbsLevel > 0);
@@ -1378,70 +1472,51 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
       uint32_t level = maxAbsLevel;
       if (maxAbsLevel > 0 && lastScanPos < 0) {
         lastScanPos = scanPos;
-        ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (scanPos >> 4) > 0) ? 2 : 0));
+        level_state_first(ls, ch, scanPos);
         cgLastScanPos = cgScanPos;
       }
       if (lastScanPos >= 0) {
-        const int oneCtx = CTX_ONE + 4 * (int)ctxSet + c1;
+        const int oneCtx = CTX_ONE + 4 * (int)ls.ctxSet + ls.c1;
         if (oneCtx != g10Ctx) { g10 = cb(oneCtx, 0); g10Ctx = oneCtx; }
-        /* position inside the 4x4 group (raster) from the packed 4x4 scan; its significance context */
-        const int p4 = (int)((scan4 >> (4 * posInCG)) & 15);
-        int ctxSig, sbit0, sbit1;
-        if (log2 == 2) { ctxSig = sigOff + (p4 ? (int)((map4 >> (4 * p4)) & 15) : 0); sbit0 = cb(ctxSig, 0); sbit1 = cb(ctxSig, 1); }
-        else if (scanPos == 0) { ctxSig = sigOff; sbit0 = cb(ctxSig, 0); sbit1 = cb(ctxSig, 1); }
-        else { const int cnt = (int)((cntBits >> (2 * p4)) & 3); ctxSig = sigBase + cnt; sbit0 = cnt == 0 ? b00 : (cnt == 1 ? b01 : b02); sbit1 = cnt == 0 ? b10 : (cnt == 1 ? b11 : b12); }
+        const int ctxSig = sig_ctx_of(S, log2, scanPos, posInCG, sigBase, cntBits);
+        int sbit0, sbit1;
+        if (log2 == 2 || scanPos == 0) { sbit0 = cb(ctxSig, 0); sbit1 = cb(ctxSig, 1); }
+        else { const int cnt = ctxSig - sigBase; sbit0 = cnt == 0 ? b00 : (cnt == 1 ? b01 : b02); sbit1 = cnt == 0 ? b10 : (cnt == 1 ? b11 : b12); }   /* one of the group's three: costs in registers */
         int sdel = 0, rup, rdn = 0;
         if (maxAbsLevel == 0) {                              /* xGetCodedLevel's early exit (:2752-2760); never the last position */
           /* short path: level 0 leaves c1/c2/Rice state alone; everything the long path does for it, and on to the next */
           cs = lambda * (double)sbit0; cc = c0 + cs;
           RdoqRec r; r.cc = cc; r.cs = cs; r.c0 = c0; r.up = g10; r.dn = 0; r.sd = sbit1 - sbit0;
           r.du = (int32_t)(levelDouble >> (qbits - 8));
-          if (SER) g_S.rq_rec[posInCG] = r; else recg[scanPos * st] = r;
+          recg[scanPos * st] = r;
           baseCost += cc;
-          if (SER) g_S.rq_lv[posInCG] = 0; else dstg[scanPos * st] = 0;
+          dstg[scanPos * st] = 0;
           rdSigCost += cs;
           if (posInCG == 0) rdSigCost0 = cs;
           continue;
         } else {
-          const int absCtx = CTX_ABS + (int)ctxSet + c2;
+          const int absCtx = CTX_ABS + (int)ls.ctxSet + ls.c2;
           LevelBits lb; lb.g10 = g10; lb.g11 = cb(oneCtx, 1); lb.g20 = cb(absCtx, 0); lb.g21 = cb(absCtx, 1);
           const int isLast = scanPos == lastScanPos;
           FCU_LV_OWN(lv_);
-#ifdef FCU_RDOQ_LEVELS_REF                                      /* level_choice_ref(), written out for the timer between its two parts */
-          int rateHi = 0, rateLo = 0;
-          LevelChoice lc; lc.rdn = 0;
-          lc.level = coded_level(cb, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, isLast ? sigOff : ctxSig, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast, &rateHi, &rateLo);
-          FCU_LV_SEC(lv_, s0);
-          if (lc.level > 0) {
-            if (lc.level == maxAbsLevel) {
-              lc.rup = ic_rate(lb, lc.level + 1, goRice, c1Idx, c2Idx) - rateHi;
-              lc.rdn = (maxAbsLevel > 1 ? rateLo : ic_rate(lb, 0, goRice, c1Idx, c2Idx)) - rateHi;
-            } else {
-              lc.rup = rateHi - rateLo;
-              lc.rdn = ic_rate(lb, lc.level - 1, goRice, c1Idx, c2Idx) - rateLo;
-            }
-          } else lc.rup = lb.g10;
-          FCU_LV_SEC(lv_, s1);
+#ifdef FCU_RDOQ_LEVELS_REF
+          const LevelChoice lc = level_choice_ref(cb, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, isLast ? sigOff : ctxSig, lb, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
 #else
-          const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
-          FCU_CHECK_LEVELS(cb, isLast ? sigOff : ctxSig, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
-          FCU_LV_SEC(lv_, s0);
+          const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
+          FCU_CHECK_LEVELS(cb, isLast ? sigOff : ctxSig, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
 #endif
+          FCU_LV_SEC(lv_, s0);
           level = lc.level; rup = lc.rup; rdn = lc.rdn;
           if (!isLast) sdel = sbit1 - sbit0;
         }
         RdoqRec r; r.cc = cc; r.cs = cs; r.c0 = c0; r.up = rup; r.dn = rdn; r.sd = sdel;
         r.du = (int32_t)((levelDouble - ((int32_t)level << qbits)) >> (qbits - 8));
-        if (SER) g_S.rq_rec[posInCG] = r; else recg[scanPos * st] = r;
+        recg[scanPos * st] = r;
         baseCost += cc;
-        const uint32_t baseLevel = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
-        if (level >= baseLevel) { if (level > 3u * (1u << goRice)) goRice = goRice + 1 < 4 ? goRice + 1 : 4; }
-        if (level >= 1) c1Idx++;
-        if (level > 1) { c1 = 0; c2 += (c2 < 2); c2Idx++; }
-        else if (c1 < 3 && c1 > 0 && level) c1++;
+        level_state_advance(ls, level);
         FCU_LV_SEC(lv_, s2);
       } else baseCost += c0;
-      if (SER) g_S.rq_lv[posInCG] = (int16_t)level; else dstg[scanPos * st] = (int16_t)level;
+      dstg[scanPos * st] = (int16_t)level;
       rdSigCost += cs;
       if (posInCG == 0) rdSigCost0 = cs;
       if (level) {
@@ -1452,53 +1527,28 @@ FCU_DEV FCU_NOINLINE RdoqOut rdoq(int c, const int32_t *src, int16_t *dst, int s
       }
     }
     FCU_LV_TOP(lv_, 0);
-    if (lastScanPos >= 0 && cgScanPos > 0) {                 /* context set of the next group (:2306-2316), once the last position is known */
-      ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (cgScanPos - 1) > 0) ? 2 : 0) + (c1 == 0));
-      c1 = 1; c2 = 0; c1Idx = 0; c2Idx = 0; goRice = 0;
-    }
-    if (cgLastScanPos >= 0) {
-      if (cgScanPos) {
-        if (((cgflag >> cgBlk) & 1) == 0) {
-          const int ctxSig = cgBase + sig_cg_ctx(cgflag, cgx, cgy, wg);
-          baseCost += lambda * (double)cb(ctxSig, 0) - rdSigCost;
-          cgg[cgScanPos * st] = lambda * (double)cb(ctxSig, 0);
-        } else if (cgScanPos < cgLastScanPos) {
-          if (nnzBeforePos0 == 0) { baseCost -= rdSigCost0; rdSigCost -= rdSigCost0; }
-          double costZeroCG = baseCost;
-          const int ctxSig = cgBase + sig_cg_ctx(cgflag, cgx, cgy, wg);
-          baseCost += lambda * (double)cb(ctxSig, 1);
-          costZeroCG += lambda * (double)cb(ctxSig, 0);
-          cgg[cgScanPos * st] = lambda * (double)cb(ctxSig, 1);
-          costZeroCG += rdUncodedDist; costZeroCG -= rdCodedLevelandDist; costZeroCG -= rdSigCost;
-          if (costZeroCG < baseCost) {
-            cgflag &= ~(1ull << cgBlk); baseCost = costZeroCG;
-            cgg[cgScanPos * st] = lambda * (double)cb(ctxSig, 0);
-            for (int posInCG = 15; posInCG >= 0; posInCG--) {
-              const int scanPos = cgScanPos * 16 + posInCG;
-              if (SER) { if (g_S.rq_lv[posInCG]) { g_S.rq_lv[posInCG] = 0; g_S.rq_rec[posInCG].cc = g_S.rq_rec[posInCG].c0; g_S.rq_rec[posInCG].cs = 0; } }
-              else if (dstg[scanPos * st]) { dstg[scanPos * st] = 0; recg[scanPos * st].cc = recg[scanPos * st].c0; recg[scanPos * st].cs = 0; }
-            }
-          }
-        }
-      } else cgflag |= 1ull << cgBlk;
-    }
-    if (SER) {                                               /* the serial variant kept the group in LDS: one burst of stores per group */
-#pragma unroll
-      for (int k = 0; k < 16; k++) { recg[(cgScanPos * 16 + k) * st] = g_S.rq_rec[k]; dstg[(cgScanPos * 16 + k) * st] = g_S.rq_lv[k]; }
+    if (lastScanPos >= 0 && cgScanPos > 0) level_state_next_group(ls, ch, cgScanPos);
+    const CgDecision cgd = cg_decide(cb, S, cgScanPos, cgLastScanPos, cgBlk, cgx, cgy, cgflag, baseCost, rdSigCost, rdSigCost0, rdCodedLevelandDist, rdUncodedDist, nnzBeforePos0);
+    cgg[cgScanPos * st] = cgd.cgSig;
+    if (cgd.zeroed) {
+      for (int posInCG = 15; posInCG >= 0; posInCG--) {
+        const int scanPos = cgScanPos * 16 + posInCG;
+        if (dstg[scanPos * st]) { dstg[scanPos * st] = 0; recg[scanPos * st].cc = recg[scanPos * st].c0; recg[scanPos * st].cs = 0; }
+      }
     }
   }
   FCU_RTOC(P, rt_, 12);                                       /* main loop */
   FCU_LV_TOP(lv_, 0); FCU_LV_END(P, lv_);
   if (lastScanPos < 0) { RdoqOut z = { 0, -1 }; return z; }
 #ifdef FCU_EMU
-  FCU_WALK_COUNT(WALK_RDOQ_ONLY_GROUP0, GRP && lastScanPos < 16);
-  if (GRP && n2 > 16 && lastScanPos >= n2 - 16) {             /* test bookkeeping: every level below the last group is 0 */
+  FCU_WALK_COUNT(WALK_RDOQ_ONLY_GROUP0, lastScanPos < 16);
+  if (n2 > 16 && lastScanPos >= n2 - 16) {                    /* test bookkeeping: every level below the last group is 0 */
     int other = 0;
     for (int sp = 0; sp < n2 - 16; sp++) other |= dstg[sp * st];
     FCU_WALK_COUNT(WALK_RDOQ_ONLY_LAST_GROUP, !other);
   }
 #endif
-  return rdoq_finish<SER>(cb, P, srcg, dstg, recg, cgg, st, log2, ch, scanType, cbfCtx, scan, scanCG, cgflag, cgLastScanPos, lastScanPos, baseCost, blockUncodedCost, lambda);
+  return rdoq_finish(cb, P, S, srcg, dstg, recg, cgg, st, log2, scanType, cbfCtx, cgflag, cgLastScanPos, lastScanPos, baseCost, blockUncodedCost);
 }
 
 /* A value every lane holds one element of, readable and writable by element from wave-uniform code: a register plus
@@ -1555,9 +1605,6 @@ __device__ inline uint32_t lane_odd16(const LaneVar<int> &f, int lb) { return (u
 __device__ inline int lane_sum(const LaneVar<int> &f) { return (int)fcu_wave_sum((uint32_t)f.r); }
 #endif
 
-#ifndef FCU_WAVE_RDOQ_MIN_LOG2
-#define FCU_WAVE_RDOQ_MIN_LOG2 2
-#endif
 /* The same quantiser for ONE block with the whole wave (called from wave-uniform code, not from inside a lane loop): the
  * un-split trial of a transform unit has a single candidate, and then a lane-private rdoq() leaves 63 lanes idle while one
  * lane walks every coefficient.  What is serial in xRateDistOptQuant's first loop is the order of the floating-point sums and
@@ -1590,16 +1637,8 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   const FCU_HBM int32_t *srcg = (const FCU_HBM int32_t *)src; FCU_HBM int16_t *dstg = (FCU_HBM int16_t *)dst;
   FCU_HBM RdoqRec *recg = (FCU_HBM RdoqRec *)rec; FCU_HBM double *cgg = (FCU_HBM double *)costCGSig;
   auto cb = [&](int ctx, int bin) -> int { return (int)FCU_EST[ctx * 2 + bin]; };
-  const int ch = comp ? 1 : 0, N = 1 << log2, n2 = N * N;
-  const int qp = comp ? P.qp_c : P.qp;
-  const int qbits = rdoq_qbits(log2, qp);
-  const double lambda = P.rdoq_lambda[comp];
-  const double errScale = P.err_scale[ch][log2 - 2];
-  const uint16_t *scan = log2 == 2 ? &g_hot.scan[scanType][0] : k_scan + k_scan_off[scanType * 4 + log2 - 2];
-  const uint8_t *scanCG = log2 <= 3 ? g_hot.scan_cg8[log2 == 2 ? 0 : scanType] : k_scan_cg + k_scan_cg_off[scanType * 4 + log2 - 2];
-  const int wg = N >> 2, firstSig = first_sig_ctx(log2, scanType, ch);
-  const int sigOff = CTX_SIG + (ch ? 28 : 0), cgBase = CTX_SIGCG + (ch ? 2 : 0);
-  const uint64_t scan4 = g_hot.scan4_nib[scanType], map4 = g_hot.map4_nib;
+  const RdoqSetup S = rdoq_setup(P, log2, comp, scanType);
+  const int ch = S.ch, n2 = S.n2, qbits = S.qbits, wg = S.wg; const double lambda = S.lambda, errScale = S.errScale;
   const int cgTop = topNZ >> 4;
   const int inRegs = log2 <= 3;                                /* the block's records stay in the lanes: scan position sp in lane sp */
   const int nStore = (cgTop + 1) << 4;                         /* the caller reads the levels of scan positions below this */
@@ -1611,9 +1650,9 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   FCU_TAIL_COUNT(TAIL_CHROMA, ch); FCU_TAIL_COUNT(TAIL_TOP_IN_GROUP0_8X8, log2 == 3 && cgTop == 0);
   /* the walk's state: wave-uniform values (the same in every lane) */
   uint64_t cgflag = 0;
-  int cgLastScanPos = -1; uint32_t ctxSet = 0; int c1 = 1, c2 = 0;
+  int cgLastScanPos = -1; LevelState ls;
   double baseCost = 0, blockUncodedCost = 0;
-  int lastScanPos = -1; uint32_t c1Idx = 0, c2Idx = 0, goRice = 0;
+  int lastScanPos = -1;
   int g10 = 0, g10Ctx = -1;
   FCU_WTIC(wt_);
   /* coefficient groups above the last candidate level: only the uncoded cost accumulates (in scan order); lanes 0..15 load and
@@ -1631,7 +1670,7 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   LaneVar<int> vCgBlk, vNext;
   LaneVar<double> vCgSig;                                      /* costCGSig of group k in lane k */
   FCU_FOR_LANES_REG {
-    if (lane <= cgTop) vCgBlk.set(lane, scanCG[lane]);
+    if (lane <= cgTop) vCgBlk.set(lane, S.scanCG[lane]);
     if (inRegs) { if (lane < nStore) vNext.set(lane, srcg[lane]); }
     else if (lane < 16) vNext.set(lane, srcg[cgTop * 16 + lane]);
   }
@@ -1642,7 +1681,7 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   for (int cgScanPos = cgTop; cgScanPos >= 0; cgScanPos--) {
     const int lb = inRegs ? cgScanPos << 4 : 0;                /* the group's sixteen lanes: lb .. lb + 15 */
     const int cgBlk = vCgBlk.get(cgScanPos), cgy = cgBlk / wg, cgx = cgBlk - cgy * wg;
-    const int sigBase = sigOff + firstSig + ((!ch && (cgx + cgy) > 0) ? 3 : 0);
+    const int sigBase = sig_base_of(S, cgx, cgy);
     const uint32_t cntBits = g_hot.cnt_bits[pattern_sig_ctx(cgflag, cgx, cgy, wg)];
     FCU_FOR_LANES_REG {
       if ((unsigned)(lane - lb) < 16u) {                       /* one coefficient of this group per lane */
@@ -1653,11 +1692,7 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
         if (maxAbsLevel > 32767u) maxAbsLevel = 32767u;
         const double err = (double)levelDouble;
         const double c0 = err * err * errScale;
-        const int p4 = (int)((scan4 >> (4 * posInCG)) & 15);
-        int ctxSig;
-        if (log2 == 2) ctxSig = sigOff + (p4 ? (int)((map4 >> (4 * p4)) & 15) : 0);
-        else if (scanPos == 0) ctxSig = sigOff;
-        else ctxSig = sigBase + (int)((cntBits >> (2 * p4)) & 3);
+        const int ctxSig = sig_ctx_of(S, log2, scanPos, posInCG, sigBase, cntBits);
         const int sbit0 = cb(ctxSig, 0), sbit1 = cb(ctxSig, 1);
         vLd.set(lane, levelDouble); vMax.set(lane, (int)maxAbsLevel); vSb0.set(lane, sbit0); vSb1.set(lane, sbit1);
         vC0.set(lane, c0); vCand.set(lane, maxAbsLevel != 0);
@@ -1669,7 +1704,6 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
     }
     const uint32_t cand = lane_nz16(vCand, lb);
     double rdSigCost = 0, rdSigCost0 = 0, rdCodedLevelandDist = 0, rdUncodedDist = 0; int nnzBeforePos0 = 0;
-    double cgSig = 0;                                          /* costCGSig of this group */
     for (int posInCG = 15; posInCG >= 0; posInCG--) {
       const int scanPos = cgScanPos * 16 + posInCG, ln = lb + posInCG;
       const int isCand = (int)((cand >> posInCG) & 1);
@@ -1678,11 +1712,11 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
       uint32_t level = 0;
       if (isCand && lastScanPos < 0) {
         lastScanPos = scanPos;
-        ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (scanPos >> 4) > 0) ? 2 : 0));
+        level_state_first(ls, ch, scanPos);
         cgLastScanPos = cgScanPos;
       }
       if (lastScanPos >= 0) {
-        const int oneCtx = CTX_ONE + 4 * (int)ctxSet + c1;
+        const int oneCtx = CTX_ONE + 4 * (int)ls.ctxSet + ls.c1;
         if (oneCtx != g10Ctx) { g10 = cb(oneCtx, 0); g10Ctx = oneCtx; }
         if (!isCand) {                                         /* level 0 leaves c1/c2/Rice state alone */
           cs = vCs.get(ln); cc = vCc.get(ln);
@@ -1696,25 +1730,21 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
         const int sbit0 = vSb0.get(ln), sbit1 = vSb1.get(ln);
         auto cbs = [&](int, int bin) -> int { return bin ? sbit1 : sbit0; };   /* the significance rates of this coefficient, looked up by its lane */
         int sdel = 0, rup, rdn = 0;
-        const int absCtx = CTX_ABS + (int)ctxSet + c2;
+        const int absCtx = CTX_ABS + (int)ls.ctxSet + ls.c2;
         LevelBits lb4; lb4.g10 = g10; lb4.g11 = cb(oneCtx, 1); lb4.g20 = cb(absCtx, 0); lb4.g21 = cb(absCtx, 1);
         const int isLast = scanPos == lastScanPos;
 #ifdef FCU_RDOQ_LEVELS_REF
-        const LevelChoice lc = level_choice_ref(cbs, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, 0, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+        const LevelChoice lc = level_choice_ref(cbs, lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, 0, lb4, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
 #else
-        const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
-        FCU_CHECK_LEVELS(cbs, 0, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb4, goRice, c1Idx, c2Idx, qbits, errScale, isLast);
+        const LevelChoice lc = level_choice(lambda, &cc, &c0, &cs, levelDouble, maxAbsLevel, sbit0, sbit1, lb4, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
+        FCU_CHECK_LEVELS(cbs, 0, lc, cc, c0, cs, lambda, levelDouble, maxAbsLevel, lb4, ls.goRice, ls.c1Idx, ls.c2Idx, qbits, errScale, isLast);
 #endif
         level = lc.level; rup = lc.rup; rdn = lc.rdn;
         if (!isLast) sdel = sbit1 - sbit0;
         vCc.put(ln, cc); vCs.put(ln, cs); vC0.put(ln, c0); vUp.put(ln, rup); vDn.put(ln, rdn); vSd.put(ln, sdel);
         vDu.put(ln, (int32_t)((levelDouble - ((int32_t)level << qbits)) >> (qbits - 8)));
         baseCost += cc;
-        const uint32_t baseLevel = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
-        if (level >= baseLevel) { if (level > 3u * (1u << goRice)) goRice = goRice + 1 < 4 ? goRice + 1 : 4; }
-        if (level >= 1) c1Idx++;
-        if (level > 1) { c1 = 0; c2 += (c2 < 2); c2Idx++; }
-        else if (c1 < 3 && c1 > 0 && level) c1++;
+        level_state_advance(ls, level);
       } else baseCost += c0;
       vLv.put(ln, (int)level);
       rdSigCost += cs;
@@ -1726,35 +1756,11 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
         if (posInCG != 0) nnzBeforePos0++;
       }
     }
-    if (lastScanPos >= 0 && cgScanPos > 0) {                   /* context set of the next group (:2306-2316), once the last position is known */
-      ctxSet = (uint32_t)((ch ? 4 : 0) + ((!ch && (cgScanPos - 1) > 0) ? 2 : 0) + (c1 == 0));
-      c1 = 1; c2 = 0; c1Idx = 0; c2Idx = 0; goRice = 0;
-    }
-    int zeroed = 0;
-    if (cgLastScanPos >= 0) {
-      if (cgScanPos) {
-        if (((cgflag >> cgBlk) & 1) == 0) {
-          const int ctxSig = cgBase + sig_cg_ctx(cgflag, cgx, cgy, wg);
-          baseCost += lambda * (double)cb(ctxSig, 0) - rdSigCost;
-          cgSig = lambda * (double)cb(ctxSig, 0);
-        } else if (cgScanPos < cgLastScanPos) {
-          if (nnzBeforePos0 == 0) { baseCost -= rdSigCost0; rdSigCost -= rdSigCost0; }
-          double costZeroCG = baseCost;
-          const int ctxSig = cgBase + sig_cg_ctx(cgflag, cgx, cgy, wg);
-          baseCost += lambda * (double)cb(ctxSig, 1);
-          costZeroCG += lambda * (double)cb(ctxSig, 0);
-          cgSig = lambda * (double)cb(ctxSig, 1);
-          costZeroCG += rdUncodedDist; costZeroCG -= rdCodedLevelandDist; costZeroCG -= rdSigCost;
-          if (costZeroCG < baseCost) {
-            cgflag &= ~(1ull << cgBlk); baseCost = costZeroCG;
-            cgSig = lambda * (double)cb(ctxSig, 0);
-            zeroed = 1;                                        /* the group's levels go to 0 (applied by their lanes below) */
-            FCU_TAIL_COUNT(TAIL_CG_ZEROED_8X8, log2 == 3);
-          }
-        }
-      } else cgflag |= 1ull << cgBlk;
-    }
-    if (zeroed) FCU_FOR_LANES_REG { if ((unsigned)(lane - lb) < 16u) vLv.set(lane, 0); }
+    if (lastScanPos >= 0 && cgScanPos > 0) level_state_next_group(ls, ch, cgScanPos);
+    const CgDecision cgd = cg_decide(cb, S, cgScanPos, cgLastScanPos, cgBlk, cgx, cgy, cgflag, baseCost, rdSigCost, rdSigCost0, rdCodedLevelandDist, rdUncodedDist, nnzBeforePos0);
+    const double cgSig = cgd.cgSig;                            /* costCGSig of this group */
+    FCU_TAIL_COUNT(TAIL_CG_ZEROED_8X8, cgd.zeroed && log2 == 3);
+    if (cgd.zeroed) FCU_FOR_LANES_REG { if ((unsigned)(lane - lb) < 16u) vLv.set(lane, 0); }   /* the group's levels go to 0, each in its lane */
     /* a larger block: records and levels of the group to the pools.  The passes that follow read the records of groups that
      * kept a level only (last position: flagged groups; sign hiding: the same): a group without one stores its sixteen zero
      * levels and nothing else.  A block in registers stores nothing here, and nothing outside this function reads its records
@@ -1792,25 +1798,9 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   {
     double bestCost = blockUncodedCost + lambda * (double)cb(cbfCtx, 0);
     baseCost += lambda * (double)cb(cbfCtx, 1);
-    const int lcc = log2 - 2, loff = ch ? 0 : (lcc * 3 + ((lcc + 1) >> 2)), lsh = ch ? lcc : ((lcc + 3) >> 2);
-    const int lbx = CTX_LASTX + (ch ? 15 : 0) + loff, lby = CTX_LASTY + (ch ? 15 : 0) + loff, lgmax = g_hot.group_idx[N - 1];
-    auto costOfLast = [&](int scanPos) -> double {             /* lane code */
-      const int blk = scan[scanPos];
-      const int py = blk >> log2, px = blk - (py << log2);
-      const int ax = scanType == 2 ? py : px, ay = scanType == 2 ? px : py;
-      const int gx = g_hot.group_idx[ax], gy = g_hot.group_idx[ay];
-      int bxs = 0, bys = 0;
-      for (int k = 0; k < gx; k++) bxs += cb(lbx + (k >> lsh), 1);
-      if (gx < lgmax) bxs += cb(lbx + (gx >> lsh), 0);
-      for (int k = 0; k < gy; k++) bys += cb(lby + (k >> lsh), 1);
-      if (gy < lgmax) bys += cb(lby + (gy >> lsh), 0);
-      double r = (double)(bxs + bys);                                  /* xGetRateLast, TComTrQuant.cpp:2898-2916 */
-      if (gx > 3) r += 32768.0 * (double)((gx - 2) >> 1);
-      if (gy > 3) r += 32768.0 * (double)((gy - 2) >> 1);
-      return lambda * r;
-    };
+    const LastCtx L = last_ctx_of(S, log2);
     LaneVar<double> wCl;
-    if (inRegs) FCU_FOR_LANES_REG { if (lane <= lastScanPos) wCl.set(lane, vLv.own(lane) ? costOfLast(lane) : 0.0); }
+    if (inRegs) FCU_FOR_LANES_REG { if (lane <= lastScanPos) wCl.set(lane, vLv.own(lane) ? rate_last(cb, S, L, log2, scanType, lane) : 0.0); }
     int foundLast = 0;
     for (int cgScanPos = cgLastScanPos; cgScanPos >= 0 && !foundLast; cgScanPos--) {
       const int lb = inRegs ? cgScanPos << 4 : 0;
@@ -1824,7 +1814,7 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
           const int lv = dstg[scanPos];
           const RdoqRec q = recg[scanPos];
           vLv.set(lane, lv); vCs.set(lane, q.cs); vCc.set(lane, q.cc); vC0.set(lane, q.c0);
-          wCl.set(lane, lv ? costOfLast(scanPos) : 0.0);
+          wCl.set(lane, lv ? rate_last(cb, S, L, log2, scanType, scanPos) : 0.0);
         }
       }
       for (int posInCG = top; posInCG >= 0; posInCG--) {
@@ -1891,20 +1881,8 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
           FCU_FOR_LANES_REG {
             const int n = lane - lb;
             long long curCost = kInf; int curChange = 0;
-            if (n >= 0 && n <= nTop) {
-              const int lv = vLv.own(lane), du = vDu.own(lane), up = vUp.own(lane), dn = vDn.own(lane), sd = vSd.own(lane);
-              if (lv != 0) {
-                const long long costUp = rdFactor * (-du) + up;
-                long long costDown = rdFactor * (du) + dn - ((iabs(lv) == 1) ? sd : 0);
-                if (lastCG == 1 && lastNZ == n && iabs(lv) == 1) costDown -= (4 << 15);
-                if (costUp < costDown) { curCost = costUp; curChange = 1; }
-                else { curChange = -1; if (n == firstNZ && iabs(lv) == 1) curCost = kInf; else curCost = costDown; }
-              } else {
-                curCost = rdFactor * (-(long long)(iabs(du))) + (1 << 15) + up + sd;
-                curChange = 1;
-                if (n < firstNZ) { const uint32_t thissign = vNext.own(lane) >= 0 ? 0 : 1; if (thissign != signbit) curCost = kInf; }
-              }
-            }
+            if (n >= 0 && n <= nTop)
+              curCost = sh_cost(vLv.own(lane), vDu.own(lane), vUp.own(lane), vDn.own(lane), vSd.own(lane), vNext.own(lane) < 0, n, firstNZ, lastNZ, lastCG, signbit, rdFactor, &curChange);
             vCostLo.set(lane, (int)(uint32_t)(unsigned long long)curCost); vCostHi.set(lane, (int)(curCost >> 32)); vChg.set(lane, curChange);
           }
           long long minCostInc = kInf; int minN = -1;
@@ -1950,7 +1928,7 @@ FCU_DEV FCU_NOINLINE void rdoq_wave(int c, const int32_t *src, int16_t *dst, int
   FCU_WTOC(P, wt_, 4, log2);
 #ifdef FCU_EMU_CHECK_RDOQ_TAIL
   if (!chkSkip) {                                              /* the serial passes on what the pool form stored */
-    const RdoqOut o = rdoq_finish<1>(cb, P, srcg, chkLv, recg, cgg, 1, log2, ch, scanType, cbfCtx, scan, scanCG, cgflag, cgLastScanPos, lastScanPos, chkBase, blockUncodedCost, lambda);
+    const RdoqOut o = rdoq_finish(cb, P, S, srcg, chkLv, recg, cgg, 1, log2, scanType, cbfCtx, cgflag, cgLastScanPos, lastScanPos, chkBase, blockUncodedCost);
     int bad = o.abs_sum != g_S.rw_abs || o.last != g_S.rw_lsp;
     for (int sp = 0; sp < nStore; sp++) bad |= chkLv[sp] != dstg[sp];
     if (bad) {
@@ -2587,13 +2565,11 @@ FCU_DEV FCU_NOINLINE void tu_trial(CuObj *cu, uint32_t tu_k, int comp, int cab, 
     FCU_TIC(t8_);
     const int cbfCtx = comp ? (CTX_CBF_CHROMA + tu.tr_depth) : (CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0));
     const int useRdoq = FCU_UNI((int)(useTS ? P.rdoq_ts : P.rdoq));
-    const int onWave = useRdoq && log2 >= FCU_WAVE_RDOQ_MIN_LOG2;      /* every size: a 4x4 / 8x8 block stays in the lanes' registers through all of rdoq_wave's passes */
-    if (onWave) rdoq_wave(cab, G->p_lscan, G->p_qscan, FCU_UNI(g_S.t_last), log2, comp, scanType, cbfCtx, P, G->r_rec, G->r_cg);
+    if (useRdoq) rdoq_wave(cab, G->p_lscan, G->p_qscan, FCU_UNI(g_S.t_last), log2, comp, scanType, cbfCtx, P, G->r_rec, G->r_cg);
     FCU_FOR_LANES {
       if (comp == 0) for (int i = lane; i < tu.nparts; i += 64) cu->tr_idx[part + i] = (uint8_t)tu.tr_depth;   /* setTrIdxSubParts */
       if (lane == 0) {
-        if (onWave) { g_S.t_abs = g_S.rw_abs; g_S.t_lsp = g_S.rw_lsp; }
-        else if (useRdoq) { const RdoqOut o = rdoq<1, 1>(cab, G->p_lscan, G->p_qscan, 1, g_S.t_last, log2, comp, scanType, cbfCtx, P, G->r_rec, G->r_cg); g_S.t_abs = o.abs_sum; g_S.t_lsp = o.last; }
+        if (useRdoq) { g_S.t_abs = g_S.rw_abs; g_S.t_lsp = g_S.rw_lsp; }
         else { const RdoqOut o = quant_plain(G->p_lscan, G->p_qscan, 1, g_S.t_last, log2, comp, P); g_S.t_abs = o.abs_sum; g_S.t_lsp = o.last; }
         E.C->n_tu_trials++;
         FCU_COUNT(E, 15, (1ull << 40) + (unsigned long long)(g_S.t_last >= 0 ? ((g_S.t_last >> 4) + 1) * 16 : 0));   /* calls : coefficient iterations */
@@ -3136,7 +3112,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_batched(CuObj *cu, uint32_t tu_k)
       const int mode = g_S.rd_mode[(lane >> tss)];
       RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
       const int cbfCtx = CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0);
-      const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq) ? rdoq<0, 1>(CAB_CUR0 + d, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, coef_scan_idx(mode, log2, 0), cbfCtx, P, rrec, rcg, lane)
+      const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq) ? rdoq<1>(CAB_CUR0 + d, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, coef_scan_idx(mode, log2, 0), cbfCtx, P, rrec, rcg, lane)
                                                             : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 0, P);
       g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last;
       g_S.vc_dist[lane] = 0;
@@ -3331,7 +3307,7 @@ FCU_DEV FCU_NOINLINE void pu_first_pass_64(CuObj *cu, uint32_t root_k)
     FCU_FOR_LANES {                                          /* RDOQ: one candidate per lane, priced against its own coder */
       if (lane < nc) {
         RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
-        const RdoqOut o = P.rdoq ? rdoq<0, 0>(CAB_LANE0 + lane, G->p_lscan + lane, G->p_qscan + lane, nc, g_S.vc_last[lane], log2, 0,
+        const RdoqOut o = P.rdoq ? rdoq<0>(CAB_LANE0 + lane, G->p_lscan + lane, G->p_qscan + lane, nc, g_S.vc_last[lane], log2, 0,
                                               coef_scan_idx(g_S.rd_mode[lane], log2, 0), CTX_CBF_LUMA + (tu.tr_depth == 0 ? 1 : 0), P, rrec, rcg, lane)
                                  : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nc, g_S.vc_last[lane], log2, 0, P);
         g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last; g_S.vc_dist[lane] = 0;
@@ -3635,7 +3611,7 @@ FCU_DEV FCU_NOINLINE void chroma_leaf_trials(CuObj *cu, uint32_t tu_k)
         const int mode = g_S.c_modes[m] == DM_CHROMA ? lumaDir : g_S.c_modes[m];
         RdoqRec *rrec = G->r_rec + lane; double *rcg = G->r_cg + lane;
         const RdoqOut o = ((lane & tss) ? P.rdoq_ts : P.rdoq)
-          ? rdoq<0, 0>(CAB_LANE0 + m, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1 /* Cb and Cr share every parameter the call reads; the argument is wave-uniform */, coef_scan_idx(mode, log2, comp), CTX_CBF_CHROMA + trDepth, P, rrec, rcg, lane)
+          ? rdoq<0>(CAB_LANE0 + m, G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1 /* Cb and Cr share every parameter the call reads; the argument is wave-uniform */, coef_scan_idx(mode, log2, comp), CTX_CBF_CHROMA + trDepth, P, rrec, rcg, lane)
           : quant_plain(G->p_lscan + lane, G->p_qscan + lane, nvc, g_S.vc_last[lane], log2, 1, P);
         g_S.vc_abs[lane] = o.abs_sum; g_S.vc_lsp[lane] = o.last;
         g_S.vc_dist[lane] = 0;
